@@ -9,6 +9,7 @@ are not stored).  Re-run:   python tests/golden/make_golden.py
 
 Cases (all eval mode, fp32, torch CPU):
   sched.npz      DDIMScheduler tables, timesteps, step() and add_noise() outputs
+  sched_cosine   DDIMScheduler(beta_schedule="squaredcos_cap_v2") tables and T=20 timesteps, 1000 and 250 training steps
   denoise_res    ScheduledCNNRefine.forward, scalar t and per-sample t          (Res variant)
   denoise_swin   ScheduledCNNRefine.forward of the Swin variant (UpSample_add fuse)
   loop_res       CNNDDIMPipiline.__call__ T=5 and T=20 (x_T injected by patching torch.randn)
@@ -99,6 +100,16 @@ def gen_sched(ref):
     nz = rs.standard_normal((B,) + tuple(c["shape"][1:])).astype(np.float32)
     s2 = ref.DDIMScheduler(num_train_timesteps=1000, clip_sample=False)
     out["add_noise"] = t2n(s2.add_noise(torch.from_numpy(x0), torch.from_numpy(nz), torch.tensor(c["add_noise_t"])))
+    return out
+
+
+def gen_sched_cosine(ref):
+    out = {}
+    for n in (1000, 250):
+        s = ref.DDIMScheduler(num_train_timesteps=n, beta_schedule="squaredcos_cap_v2", clip_sample=False)
+        out[f"betas_n{n}"], out[f"alphas_cumprod_n{n}"] = s.betas.numpy().copy(), s.alphas_cumprod.numpy().copy()
+        s.set_timesteps(20)
+        out[f"timesteps_n{n}_T20"] = np.asarray(s.timesteps).copy()
     return out
 
 
@@ -311,6 +322,7 @@ def main():
     torch.set_num_threads(8)
     gens = {
         "sched": lambda: gen_sched(ref),
+        "sched_cosine": lambda: gen_sched_cosine(ref),
         "denoise_res": lambda: gen_denoise(ref, "denoise_res"),
         "denoise_swin": lambda: gen_denoise(ref, "denoise_swin"),
         "denoise_bwd_res": lambda: gen_denoise_bwd(ref, "denoise_bwd_res"),

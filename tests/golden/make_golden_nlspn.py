@@ -20,6 +20,7 @@ Cases -> tests/golden/nlspn_<name>.npz
   k5         prop_kernel 5 (24 neighbours), TGASS, prop_time 2
   dcn_*      plain modulated_deform_conv forward/backward cases (groups, deformable groups, stride, dilation) straight from the
              reference kernels, for the general DCNv2 entry points
+  dcn_device_cases   the seeded cases of tests/test_oracle_dcn.py (inputs + the reference kernels' forward / gradients)
 """
 from __future__ import annotations
 
@@ -127,6 +128,27 @@ def dcn_case(name, seed, B, C, Co, H, W, kh, kw, stride, pad, dil, group, dg, st
     print(f"dcn_{name}: out {y.shape}")
 
 
+def device_code_cases():
+    """tests/test_oracle_dcn.py's seeded cases (SHAPES, and the pad_h / pad_w case of the col2im launcher slip) through the reference's device code:
+    inputs and the reference's outputs -> dcn_device_cases.npz"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import test_oracle_dcn as T
+    out = {}
+    for i, shape in enumerate(T.SHAPES):
+        B, C, Co, H, W, kh, kw, st, pd, dl, grp, dg = shape
+        c = T._rand_case(np.random.RandomState(hash(shape) % 2**31), *shape)
+        out.update({f"case{i}_{k}": v for k, v in c.items()})
+        out[f"case{i}_out"] = dcn_ref.forward(c["x"], c["w"], c["b"], c["off"], c["m"], st, pd, dl, grp, dg, im2col_step=1)
+        g = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
+        out.update({f"case{i}_g_{k}": v for k, v in zip(T.GRAD_NAMES, g)})
+    shape = T.SLIP_SHAPE
+    c = T._rand_case(np.random.RandomState(5), *shape)
+    out.update({f"slip_{k}": v for k, v in c.items()})
+    out["slip_g_input"] = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], shape[7], shape[8], shape[9], 1, 1)[0]
+    np.savez_compressed(os.path.join(HERE, "dcn_device_cases.npz"), **out)
+    print(f"dcn_device_cases: {len(T.SHAPES)} cases + the slip case")
+
+
 def main():
     NLSPN, _ = load_reference_nlspn()
     torch.manual_seed(0)
@@ -138,6 +160,7 @@ def main():
     dcn_case("groups", 21, 2, 4, 6, 7, 9, 3, 3, (1, 1), (1, 1), (1, 1), 2, 1, 1)
     dcn_case("dg_stride", 22, 2, 4, 4, 9, 8, 3, 3, (2, 1), (1, 1), (1, 2), 1, 2, 2)
     dcn_case("k1", 23, 3, 2, 3, 6, 5, 1, 1, (1, 1), (0, 0), (1, 1), 1, 1, 64)
+    device_code_cases()
 
 
 if __name__ == "__main__":

@@ -1,6 +1,7 @@
 """CPU: the NLSPN / DCNv2 oracle (oracle/dcn_oracle.py) is pinned to the reference:
   (1) against the reference's OWN device code compiled for the host (oracle/_ref/libref_dcn.so, built by oracle/ref_dcn/build_ref.py
-      from /root/reference/src/model/deformconv/src/cuda/modulated_deform_im2col_cuda.cuh) on seeded random cases;
+      from the reference's src/model/deformconv/src/cuda/modulated_deform_im2col_cuda.cuh) on seeded random cases, its results recorded in
+      tests/golden/dcn_device_cases.npz (tests/golden/make_golden_nlspn.py);
   (2) against goldens minted by running the reference's NLSPN class / DCN kernels on CPU (tests/golden/make_golden_nlspn.py);
   (3) against the known answers of the reference's own self-test (src/model/deformconv/test.py): zero offsets == nn.Conv2d
       (check_mdconv_zero_offset, :68-110), identity kernel (check_mdconv_zero_offset_identify, :140-177), im2col_step
@@ -15,7 +16,7 @@ import numpy as np
 import pytest
 import torch
 
-from oracle import dcn_oracle as O, dcn_ref
+from oracle import dcn_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 2e-6
@@ -36,27 +37,34 @@ def _rand_case(rs, B, C, Co, H, W, kh, kw, st, pd, dl, grp, dg):
 SHAPES = [(2, 4, 4, 5, 6, 3, 3, (1, 1), (1, 1), (1, 1), 2, 1), (2, 4, 6, 7, 5, 3, 3, (2, 1), (1, 1), (1, 2), 1, 2),
           (1, 1, 1, 9, 11, 3, 3, (1, 1), (1, 1), (1, 1), 1, 1), (2, 1, 1, 6, 7, 1, 1, (1, 1), (0, 0), (1, 1), 1, 1),
           (1, 2, 2, 8, 8, 5, 5, (1, 1), (2, 2), (1, 1), 1, 1)]
+SLIP_SHAPE = (1, 2, 2, 6, 9, 3, 3, (1, 1), (1, 2), (1, 1), 1, 1)
+GRAD_NAMES = ("input", "offset", "mask", "weight", "bias")
 
 
-@pytest.mark.skipif(not dcn_ref.available(), reason="neither oracle/_ref/libref_dcn.so nor /root/reference present")
+def _device_case(golden, tag):
+    """inputs (_rand_case's keys) and the reference device code's results of one recorded case (tests/golden/make_golden_nlspn.py)"""
+    g = golden("dcn_device_cases")
+    return {k[len(tag) + 1:]: v for k, v in g.items() if k.startswith(tag + "_")}
+
+
 @pytest.mark.parametrize("shape", SHAPES, ids=[f"case{i}" for i in range(len(SHAPES))])
-def test_oracle_matches_reference_device_code(shape):
+def test_oracle_matches_reference_device_code(golden, shape):
     B, C, Co, H, W, kh, kw, st, pd, dl, grp, dg = shape
-    c = _rand_case(np.random.RandomState(hash(shape) % 2**31), *shape)
-    y_ref = dcn_ref.forward(c["x"], c["w"], c["b"], c["off"], c["m"], st, pd, dl, grp, dg, im2col_step=1)
+    c = _device_case(golden, f"case{SHAPES.index(shape)}")
+    assert c["x"].shape == (B, C, H, W) and c["w"].shape == (Co, C // grp, kh, kw)
+    y_ref = c["out"]
     assert rel(O.mdcn_forward(c["x"], c["w"], c["b"], c["off"], c["m"], st, pd, dl, grp, dg), y_ref) < TOL
-    g_ref = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
+    g_ref = [c["g_" + name] for name in GRAD_NAMES]
     g_or = O.mdcn_backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
-    for name, a, r in zip(("input", "offset", "mask", "weight", "bias"), g_or, g_ref):
+    for name, a, r in zip(GRAD_NAMES, g_or, g_ref):
         assert rel(a, r) < TOL, name
 
 
-@pytest.mark.skipif(not dcn_ref.available(), reason="neither oracle/_ref/libref_dcn.so nor /root/reference present")
-def test_reference_col2im_uses_pad_h_for_both_paddings():
+def test_reference_col2im_uses_pad_h_for_both_paddings(golden):
     """The launcher slip (modulated_deform_im2col_cuda.cuh:372): only visible when pad_h != pad_w; the oracle reproduces it."""
-    shape = (1, 2, 2, 6, 9, 3, 3, (1, 1), (1, 2), (1, 1), 1, 1)
-    c = _rand_case(np.random.RandomState(5), *shape)
-    g_ref = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], shape[7], shape[8], shape[9], 1, 1)[0]
+    shape = SLIP_SHAPE
+    c = _device_case(golden, "slip")
+    g_ref = c["g_input"]
     g_slip = O.mdcn_backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], shape[7], shape[8], shape[9], 1, 1, pad_w_slip=True)[0]
     g_math = O.mdcn_backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], shape[7], shape[8], shape[9], 1, 1, pad_w_slip=False)[0]
     assert rel(g_slip, g_ref) < TOL

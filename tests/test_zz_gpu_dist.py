@@ -44,10 +44,20 @@ print("RCCL-ONE-RANK-OK")
 """
 
 
+def _reserved_port():
+    """A socket bound to a free port of 127.0.0.1 (SO_REUSEADDR, never listening); the port is its getsockname()[1].  Held open while the child
+    runs, it keeps the port from being handed to any other process in the seconds before the child's store listens on it -- a bare bind and
+    close let the launcher's rendezvous fail with EADDRINUSE on a busy host.  The store listens beside it (it sets SO_REUSEADDR as well)."""
+    s = socket.socket()
+    s.setsockopt(socket.SOL_SOCKET, socket.SO_REUSEADDR, 1)
+    s.bind(("127.0.0.1", 0))
+    return s
+
+
 def test_rccl_process_group_gradient_allreduce_and_sync_batchnorm_on_one_rank():
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-    env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", DD_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, timeout=300)
+    with _reserved_port() as s:
+        env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(s.getsockname()[1]), RANK="0", WORLD_SIZE="1", DD_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
+        r = subprocess.run([sys.executable, "-c", SCRIPT], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "RCCL-ONE-RANK-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
 
 
@@ -96,10 +106,10 @@ def test_lanes_run_concurrently_in_a_process_whose_rccl_communicator_came_first(
     runtime put a lane's new stream on the caller's own hardware queue (GPU_MAX_HW_QUEUES = 4 queues, the least-used one handed out once they exist) and the
     two lanes serialised: the KITTI step ran 23 % slower than concurrent lanes (profiles/r06_experiments.md section 9).  The library now probes a lane's
     stream for concurrency with the caller's when it creates it (dd_api.cpp: acquire_lane_stream) and replaces one that failed."""
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
-    env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", DD_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, "-c", LANES_SCRIPT], env=env, capture_output=True, text=True, timeout=400)
+    with _reserved_port() as s:
+        env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(s.getsockname()[1]), RANK="0", WORLD_SIZE="1", DD_ROOT=ROOT, HSA_ENABLE_IPC_MODE_LEGACY="0")
+        r = subprocess.run([sys.executable, "-c", LANES_SCRIPT], env=env, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0 and "LANES-OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
     import gpu_util
     gpu_util.record("lanes_after_rccl", line=[l for l in r.stdout.splitlines() if l.startswith("LANES one")][-1])
@@ -111,10 +121,10 @@ def _bench(argv, launcher, timeout=600):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     cmd = [sys.executable]
-    if launcher:
-        s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
-        cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    r = subprocess.run(cmd + [os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    with _reserved_port() as s:
+        if launcher:
+            cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(s.getsockname()[1])]
+        r = subprocess.run(cmd + [os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True, timeout=timeout, cwd=ROOT)
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     return r, (json.loads(lines[-1]) if lines else None)
 

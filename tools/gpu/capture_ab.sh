@@ -1,5 +1,5 @@
 cd /root/repo
-X="--steps 20 --warmup 3 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-streams-extra --no-abs-extra"
+X="--full --steps 20 --warmup 3 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-streams-extra --no-abs-extra"
 pick() { python -c "
 import sys, json
 for l in sys.stdin:

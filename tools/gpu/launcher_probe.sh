@@ -3,7 +3,7 @@
 # tools/rccl_slowdown_probe.py)  Arms: plain; the process-group path without the launcher (WORLD_SIZE=1 in the environment); the same with OMP_NUM_THREADS=1; the launcher;
 # the launcher's environment replayed without the launcher.
 cd "$(dirname "$0")/../.."; mkdir -p gpurun_out
-X="--steps 10 --warmup 2 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra --no-abs-extra"
+X="--full --steps 10 --warmup 2 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra --no-abs-extra"
 pick() { python -c "
 import sys, json
 for l in sys.stdin:
@@ -22,7 +22,7 @@ import json, os, subprocess, sys
 child = json.load(open("gpurun_out/launcher_env.json"))
 new = {k: v for k, v in child.items() if os.environ.get(k) != v}
 print("variables the launcher adds / changes:", json.dumps({k: v[:60] for k, v in new.items()}))
-X = "--steps 10 --warmup 2 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra --no-abs-extra".split()
+X = "--full --steps 10 --warmup 2 --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra --no-abs-extra".split()
 def run(tag, env):
     e = dict(os.environ); e.update(env); e["MASTER_PORT"] = "29570"
     out = subprocess.run([sys.executable, "bench.py", "--gpus", "1"] + X, env=e, capture_output=True, text=True, timeout=300).stdout

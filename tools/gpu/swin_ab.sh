@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of library variants on the Swin denoiser: parity tests of the Swin paths, then the bench line (one stream) twice per variant, alternating
 cd "$(dirname "$0")/../.."; mkdir -p gpurun_out; export TMPDIR=/tmp
-X="--no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra"
+X="--full --no-cpu-baseline --no-train-extra --no-nlspn-extra --no-head-extra --no-latency-b1 --no-streams-extra"
 for n in "$@"; do
   DDEPTH_LIBRARY=$PWD/build_variants/libddepth_$n.so timeout 600 python -m pytest tests/test_gpu_parity.py tests/test_gpu_backward.py -m gpu -q -x -k "swin" -p no:cacheprovider 2>&1 | tail -n 2
 done
