@@ -23,11 +23,14 @@ from .head import (DDIMDepthEstimate_Res, DDIMDepthEstimate_Swin_ADD, DDIMDepthE
 from .necks import HAHIHeteroNeck
 from .nlspn import NLSPN
 from .model import Diffusion_DCbase_Model
+from .metric import Diffusion_DCbase_Metric, MetricAccumulator
+from .loss import Diffusion_DCbase_Loss
 
 __all__ = [
     "DDIMScheduler", "HipDenoiser", "precision_id", "library_path", "load_library",
     "ScheduledCNNRefine", "CNNDDIMPipiline", "DeepDepthTransformWithUpsampling",
     "DDIMDepthEstimate_Res", "DDIMDepthEstimate_Swin_ADD", "DDIMDepthEstimate_Swin_ADDHAHI", "DDIMDepthEstimate_MPVIT_ADDHAHI",
     "DDIMDepthEstimate_ResVis", "DDIMDepthEstimate_Swin_ADDHAHIVis", "HAHIHeteroNeck", "NLSPN", "Diffusion_DCbase_Model",
+    "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
 ]
 __version__ = "0.1.0"
