@@ -306,63 +306,46 @@ static int condition_impl(dd_handle_t h, const float* const* feats, const int* f
     if (rc) return rc;
   }
 
-  auto launch = [&](int layer, const ConvParams& q) -> hipError_t {
-    if (!h->layer_timing) return launch_conv_igemm2(layer, kk, q, s);
-    hipEvent_t a, b;
-    hipError_t e = hipEventCreate(&a); if (e != hipSuccess) return e;
-    e = hipEventCreate(&b); if (e != hipSuccess) return e;
-    (void)hipEventRecord(a, s);
-    e = launch_conv_igemm2(layer, kk, q, s);
-    (void)hipEventRecord(b, s);
-    h->pending_ev.emplace_back(layer - 1, a, b);
-    return e;
-  };
+  const int P = pyramid_of(h->variant, h->fpn_pyramid);
   // top-down pass (reference ...res.py:108-118): x_3 = lat_3(f_3);  x_i = lat_i(f_i) + pool(up_i(x_{i+1}))
   for (int i = FPN_LEVELS - 1; i >= 0; --i) {
     const int hh = feat_h[i], ww = feat_w[i];
     DD_HIP(launch_nchw_to_nhwc_padded(feats[i], fw->fin[i].p, ok, B, fpn_cin(h->variant, h->fpn_pyramid)[i],
                                       fpn_cin_pad(h->variant, h->fpn_pyramid)[i], hh, ww, 1, s));
-    const int lat_layer = fpn_lat_layer(h->variant, h->fpn_pyramid, i);
+    const int lat_layer = kid_fpn_lateral(P, i);
     const void* lat_in = fw->fin[i].p;
     if (with_neck) {
       // HAHI neck of level i (reference hahi.py:170-173,196-197,226-272; attention off): l = lateral(x); e = proj(l);
       // out = fusion(cat) with cat = [e | l] at level 0 (hahi.py:249: cat([fusion_res_conv, feat_conv])) and [l | e] above (:262)
       const int C = neck_ck(h->fpn_pyramid, i), CT = C + 512, l_off = (i == 0) ? 512 : 0, e_off = (i == 0) ? 0 : C;
-      const int nb = neck_base(h->fpn_pyramid);
       ConvParams q{};
       q.B = B; q.h = hh; q.w = ww;
-      q.tiles_x = (ww + 31) / 32;
-      q.tiles_y = (hh + 7) / 8;
       q.in = fw->fin[i].p; q.in_cstride = C; q.in_coff = 0;
       q.out = fw->nk_cat[i].p; q.out_cstride = CT; q.out_coff = l_off;
       q.wpack = h->neck_w[i][wk].p; q.bias = h->neck_b[i].as<float>();
-      DD_HIP(launch(nb + i, q));
+      DD_TRY(launch_conv(h, kid_neck(P, NECK_LATERAL, i), kk, q, s, kid_neck(P, NECK_LATERAL, i)));
       q.in = fw->nk_cat[i].p; q.in_cstride = CT; q.in_coff = l_off;
       q.out = fw->nk_cat[i].p; q.out_cstride = CT; q.out_coff = e_off;
       q.wpack = h->neck_w[4 + i][wk].p; q.bias = h->neck_b[4 + i].as<float>();
-      DD_HIP(launch(nb + 4 + i, q));
+      DD_TRY(launch_conv(h, kid_neck(P, NECK_PROJ, i), kk, q, s, kid_neck(P, NECK_PROJ, i)));
       q.in = fw->nk_cat[i].p; q.in_cstride = CT; q.in_coff = 0;
       q.out = fw->nk_out[i].p; q.out_cstride = C; q.out_coff = 0;
       q.wpack = h->neck_w[8 + i][wk].p; q.bias = h->neck_b[8 + i].as<float>();
-      DD_HIP(launch(nb + 8 + i, q));
+      DD_TRY(launch_conv(h, kid_neck(P, NECK_FUSION, i), kk, q, s, kid_neck(P, NECK_FUSION, i)));
       h->n_neck_launches += 3;
       lat_in = fw->nk_out[i].p;
     }
     ConvParams p{};
     p.B = B; p.h = hh; p.w = ww;
-    p.tiles_x = (ww + 31) / 32;
-    p.tiles_y = (hh + conv_pack_geom2(lat_layer, kk).th - 1) / conv_pack_geom2(lat_layer, kk).th;
     p.in = lat_in; p.wpack = h->fpn_lat_w[i][wk].p; p.bias = h->fpn_lat_b[i].as<float>();
     p.out = (i == 0) ? cbuf->p : fw->lat[i].p;
     p.addend = (i == FPN_LEVELS - 1) ? nullptr : (fw->pooled[i].p ? fw->pooled[i].p : fw->up[i].p);
-    DD_HIP(launch(lat_layer, p));
+    DD_TRY(launch_conv(h, lat_layer, kk, p, s, lat_layer));
     if (i > 0) {
       ConvParams u{};
       u.B = B; u.h = hh; u.w = ww;
-      u.tiles_x = (ww + 31) / 32;
-      u.tiles_y = (hh + conv_pack_geom2(14, kk).th - 1) / conv_pack_geom2(14, kk).th;
       u.in = fw->lat[i].p; u.wpack = h->fpn_up_w[i - 1][wk].p; u.bias = h->fpn_up_b[i - 1].as<float>(); u.out = fw->up[i - 1].p;
-      DD_HIP(launch(14, u));
+      DD_TRY(launch_conv(h, KID_FPN_UP, kk, u, s, KID_FPN_UP));
       if (fw->pooled[i - 1].p)
         DD_HIP(launch_adaptive_pool_blocked(fw->up[i - 1].p, fw->pooled[i - 1].p, ok, B, COND_C, 2 * hh, 2 * ww, feat_h[i - 1], feat_w[i - 1], s));
     }

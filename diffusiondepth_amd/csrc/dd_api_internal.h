@@ -8,6 +8,7 @@
 #pragma once
 #include "../../include/ddepth.h"
 #include "dd_kernels.h"
+#include "dd_kernel_ids.h"
 
 #include <cmath>
 #include <cstdio>
@@ -62,7 +63,7 @@ constexpr int WIMG_SPLIT = 3; // and conv4 a fifth: the f16 image with the weigh
 constexpr int WIMG_STACK = 4;
 inline int wimg_kind(int slot) { return slot == WIMG_SPLIT ? (int)EK_F16S : slot == WIMG_STACK ? (int)EK_F16R : slot; }     // image slot -> kind handed to the packers / conv_pack_geom2
 inline int wimg_slot(int kind) { return kind == EK_F16S ? WIMG_SPLIT : kind; }
-inline bool wimg_has(int slot, int fwd_layer) { return slot != WIMG_STACK || fwd_layer == 4; }     // which convolution carries which image
+inline bool wimg_has(int slot, int fwd_layer) { return slot != WIMG_STACK || fwd_layer == KID_CONV4; }     // which convolution carries which image
 // precision -> element kind / mode of the fused kernels.  DD_PREC_BF16 is the mode EK_BF16M (bf16 operands on the large convolutions, f16
 // storage and thin layers: dd_kernels.h) unless the handle option "bf16_storage" = 1 selects all-bf16 tensors (A/B and error budget).
 inline int ek_of_precision(int prec, bool bf16_pure) {
@@ -79,7 +80,6 @@ inline size_t ek_size(int ek) { return (ek == EK_F32 || ek == EK_F16S) ? 4 : 2; 
 inline int thin_kind(int ek) { return ek == EK_BF16M ? (int)EK_F16 : ek; }      // conv1 / conv4 / once-per-image conv3(cond): kernels and weights
 constexpr int DD_PREC_LAST = DD_PREC_F16R;
 
-constexpr int FPN_LEVELS = 4;
 constexpr int FPN_CIN_RES[FPN_LEVELS] = {64, 128, 256, 512};       // ResNet pyramid widths (reference ...res.py:31 in_channels)
 constexpr int FPN_CIN_SWIN[FPN_LEVELS] = {192, 384, 768, 1536};   // Swin-L pyramid widths (reference ...res_swin_add.py:31)
 // MPViT-small pyramid of DDIMDepthEstimate_MPVIT_ADDHAHI (reference src/model/head/ddim_depth_estimate_res_mpvit_HAHI.py:32); same
@@ -87,22 +87,19 @@ constexpr int FPN_CIN_SWIN[FPN_LEVELS] = {192, 384, 768, 1536};   // Swin-L pyra
 // carried with 224 channels (8 zero channels, zero weights).  The pyramid is recognised from the lateral weights' sizes (dd_set_weight).
 constexpr int FPN_CIN_MPVIT[FPN_LEVELS] = {128, 216, 288, 288};
 constexpr int FPN_CIN_MPVIT_PAD[FPN_LEVELS] = {128, 224, 288, 288};
-constexpr int FPN_LAYER_MPVIT[FPN_LEVELS] = {24, 25, 26, 26};
 enum { PYR_DEFAULT = 0, PYR_MPVIT = 1 };
+inline int pyramid_of(int variant, int pyr) { return pyr == PYR_MPVIT ? PYRAMID_MPVIT : variant == DD_VARIANT_SWIN ? PYRAMID_SWIN : PYRAMID_RES; }      // -> dd::Pyramid (dd_kernel_ids.h)
 inline const int* fpn_cin(int variant, int pyr) {
   return pyr == PYR_MPVIT ? FPN_CIN_MPVIT : (variant == DD_VARIANT_SWIN ? FPN_CIN_SWIN : FPN_CIN_RES);
 }
 inline const int* fpn_cin_pad(int variant, int pyr) { return pyr == PYR_MPVIT ? FPN_CIN_MPVIT_PAD : fpn_cin(variant, pyr); }
-inline int fpn_lat_layer(int variant, int pyr, int level) {      // kernel layer id
-  return pyr == PYR_MPVIT ? FPN_LAYER_MPVIT[level] : (variant == DD_VARIANT_SWIN ? 15 : 10) + level;
-}
 
 struct ConvLayer {                  // one Conv3x3 + its following GroupNorm
   int cin = 0, cout = 0;
   DevBuf wpack2[NUM_WIMG];          // packed for the fused kernels (pre-swizzled for LDS-DMA)
   DevBuf bias;                      // [cout padded to 32]
   DevBuf w_oihw;                    // naive path
-  DevBuf wpackT[NUM_EK];            // fused backward: W' packed for the dgrad layer (23 - conv index) of dd_igemm2.hip
+  DevBuf wpackT[NUM_EK];            // fused backward: W' packed for the dgrad layer (kid_dgrad(conv index)) of dd_igemm2.hip
   DevBuf wT_oihw;                   // naive backward: W'[ci][co][ky][kx] = W[co][ci][2-ky][2-kx] (dgrad as a forward conv)
   DevBuf gamma, beta;               // GroupNorm affine [cout]
 };
@@ -177,23 +174,22 @@ struct FpnWork {
 };
 
 
-// The HAHI neck's convolutions (reference src/model/necks/hahi.py:60-97; attention off): kernel layer base + 4 * kind + level, base 30 for
-// the Swin-L pyramid (192 << level channels), 54 for MPViT-small (128 | 216 | 288 | 288; the kernels carry 216 as 224 channels).
+// The HAHI neck's convolutions (reference src/model/necks/hahi.py:60-97; attention off): kernel ids kid_neck(pyramid, kind, level)
+// (dd_kernel_ids.h) for the Swin-L pyramid (192 << level channels) and MPViT-small (128 | 216 | 288 | 288; the kernels carry 216 as 224 channels).
 // cout / cin = the reference tensors' sizes; C = real channels of the level, Ck = channels the kernels carry.
 struct NeckConv { int layer; std::string name; int cout, cin, ks, level, kind, C, Ck; };
 constexpr int NECK_C_MPVIT[4] = {128, 216, 288, 288};
 inline int neck_c(int pyr, int level) { return pyr == PYR_MPVIT ? NECK_C_MPVIT[level] : (192 << level); }
 inline int neck_ck(int pyr, int level) { return pyr == PYR_MPVIT ? FPN_CIN_MPVIT_PAD[level] : (192 << level); }
-inline int neck_base(int pyr) { return pyr == PYR_MPVIT ? 54 : 30; }
 inline std::vector<NeckConv> neck_convs(int pyr) {
   std::vector<NeckConv> v;
-  const int base = neck_base(pyr);
+  const int P = pyramid_of(DD_VARIANT_SWIN, pyr);
   for (int i = 0; i < 4; ++i) {
     const int C = neck_c(pyr, i), Ck = neck_ck(pyr, i);
     const std::string si = std::to_string(i), sj = std::to_string(i - 1);
-    v.push_back({base + i, "hahineck.lateral_convs." + si, C, C, 1, i, 0, C, Ck});
-    v.push_back({base + 4 + i, i == 0 ? std::string("hahineck.conv_proj.0") : "hahineck.trans_proj." + sj, 512, C, 1, i, 1, C, Ck});
-    v.push_back({base + 8 + i, i == 0 ? std::string("hahineck.conv_fusion.0") : "hahineck.trans_fusion." + sj, C, C + 512, 3, i, 2, C, Ck});
+    v.push_back({kid_neck(P, NECK_LATERAL, i), "hahineck.lateral_convs." + si, C, C, 1, i, NECK_LATERAL, C, Ck});
+    v.push_back({kid_neck(P, NECK_PROJ, i), i == 0 ? std::string("hahineck.conv_proj.0") : "hahineck.trans_proj." + sj, 512, C, 1, i, NECK_PROJ, C, Ck});
+    v.push_back({kid_neck(P, NECK_FUSION, i), i == 0 ? std::string("hahineck.conv_fusion.0") : "hahineck.trans_fusion." + sj, C, C + 512, 3, i, NECK_FUSION, C, Ck});
   }
   return v;
 }
@@ -278,7 +274,7 @@ struct dd_handle_s {
   std::map<std::tuple<int, int, int, int, int>, std::pair<std::shared_ptr<DevBuf>, uint64_t>> cond_bufs;   // (B, h, w, precision, lane) -> buffer, last use
   // condition FPN (Res variant): folded + packed weights, workspace of the last shape, and where its result lives
   bool neck_committed = false;            // hahineck.* folded + packed (DD_VARIANT_SWIN with the Swin-L pyramid only)
-  DevBuf neck_w[12][NUM_WIMG], neck_b[12];  // index = kernel layer - 30 (Swin-L pyramid) / - 54 (MPViT-small): 4 * kind + level
+  DevBuf neck_w[NECK_CONVS][NUM_WIMG], neck_b[NECK_CONVS];  // index = 4 * kind + level (kernel id - kid_neck_base(pyramid))
   int64_t n_neck_launches = 0;
   bool fpn_committed = false;
   int fpn_pyramid = PYR_DEFAULT;  // PYR_MPVIT once MPViT-sized lateral weights were set (DD_VARIANT_SWIN only)
@@ -297,8 +293,8 @@ struct dd_handle_s {
   bool ev_valid = false;
   hipStream_t cap_stream = nullptr;   // capture-only stream (torch's default stream is the NULL stream, which cannot capture)
   int64_t n_graph_launches = 0, n_eager_loops = 0, n_capture_failures = 0;
-  static constexpr int N_LAYER_SLOTS = 72;   // kernel layer ids run up to 65 (see dd_igemm2_cfg.h)
-  double layer_ms[N_LAYER_SLOTS] = {0};     // index = kernel layer id - 1 (1..4 Res, 5..7 Swin fuse, 8..9 hoisted conv3, 10..18 / 24..26 condition FPN, 20..23 dgrad)
+  static constexpr int N_LAYER_SLOTS = KID_LAST;   // one slot per kernel id (dd_kernel_ids.h)
+  double layer_ms[N_LAYER_SLOTS] = {0};     // index = kernel id - 1; a special form books under the id the caller launched it as (launch_conv's slot)
   int64_t layer_cnt[N_LAYER_SLOTS] = {0};
   std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> pending_ev;
 
@@ -312,6 +308,8 @@ struct dd_handle_s {
       return h->fail(DD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));              \
   } while (0)
 
+#define DD_TRY(expr) do { int _rc = (expr); if (_rc != DD_OK) return _rc; } while (0)      // a call that has already recorded its error (h->fail)
+
 // ---- functions shared between the units (defined in the unit named) ----
 namespace ddapi {
 struct WeightSpec { std::string name; int64_t numel; };
@@ -324,6 +322,7 @@ constexpr int kCins[4] = {LATENT_C, HID_C, COND_C, HID_C}, kCouts[4] = {HID_C, C
 int weight_group(const std::string& name);
 std::vector<WeightSpec> required_weights(int variant, int pyr = PYR_DEFAULT);
 bool pack_conv_weights(const float* w_oihw, const PackGeom& g, int ek, bool swizzle, std::vector<uint8_t>& out);
+int pack_geom(dd_handle_t h, int kid, int ek, PackGeom* g);      // conv_pack_geom2, failing the call for a pair no kernel runs
 int upload(dd_handle_t h, DevBuf& dst, const void* src, size_t bytes, hipStream_t s);
 int pull_device_weights_to_host(dd_handle_t h, hipStream_t s);
 int ensure_bytes(dd_handle_t h, DevBuf& dst, size_t bytes);
@@ -339,6 +338,22 @@ int want_hoist(dd_handle_t h, int precision, int T = 1, int keep = 0);
 bool keep2_fits(dd_handle_t h, size_t need);
 bool plan_big_tiles(dd_handle_t h, const PlanKey& key);
 int get_plan(dd_handle_t h, const PlanKey& key, Plan** out);
+// Launches kernel (kid, ek) on the image p.B x p.h x p.w: fills p's tile counts from the geometry of that pair, fails the call when no kernel runs
+// it, and with option "layer_timing" books the launch's time under kernel id `slot` (0 = not timed).
+bool conv_tiles(ConvParams& p, int kid, int ek);      // false: the pair has no kernel
+int launch_conv(dd_handle_t h, int kid, int ek, ConvParams p, hipStream_t s, int slot = 0);
+// `launch()` between the event pair of option "layer_timing", booked under kernel id `slot` (0 / option off: just launch())
+template <class F> hipError_t timed(dd_handle_t h, int slot, hipStream_t s, F launch) {
+  if (!h->layer_timing || slot <= 0) return launch();
+  hipEvent_t a, b;
+  hipError_t e = hipEventCreate(&a); if (e != hipSuccess) return e;
+  e = hipEventCreate(&b); if (e != hipSuccess) return e;
+  (void)hipEventRecord(a, s);
+  e = launch();
+  (void)hipEventRecord(b, s);
+  h->pending_ev.emplace_back(slot - 1, a, b);
+  return e;
+}
 int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, float* x_out, bool apply_update,
                        const long long* tvec, int t_base, int t_bstride, hipStream_t s);
 int enqueue_naive_eps(dd_handle_t h, Plan* pl, int step, const float* x_in, const long long* tvec, int t_base,

@@ -128,13 +128,26 @@ bool plan_big_tiles(dd_handle_t h, const PlanKey& key) {
   const bool many = (long long)key.B * ((key.h + 7) / 8) * ((key.w + 31) / 32) > h->resident_slots;
   return many && h->variant == DD_VARIANT_SWIN;
 }
-inline int conv3c_kid(dd_handle_t h, const PlanKey& key) { return plan_big_tiles(h, key) ? (int)BIG_CONV3C : 8; }
+inline int conv3c_kid(dd_handle_t h, const PlanKey& key) { return plan_big_tiles(h, key) ? (int)BIG_CONV3C : KID_CONV3C; }
 // the loop's hoisted conv3: 16x32 tiles, or 8x32 tiles -- with ONE patch buffer (kernel id ONE_CONV3H: same tiles, same fragment order, 52 KB
 // of LDS = three workgroups per CU) when there are more tiles than the chip holds at two per CU
 inline int conv3h_kid(dd_handle_t h, const PlanKey& key) {
   if (plan_big_tiles(h, key)) return (int)BIG_CONV3H;
   const bool many = (long long)key.B * ((key.h + 7) / 8) * ((key.w + 31) / 32) > h->resident_slots;
-  return (h->one_buffer == 2 || (many && h->one_buffer)) ? (int)ONE_CONV3H : 9;      // (2 = always: tests)
+  return (h->one_buffer == 2 || (many && h->one_buffer)) ? (int)ONE_CONV3H : KID_CONV3H;      // (2 = always: tests)
+}
+
+bool conv_tiles(ConvParams& p, int kid, int ek) {
+  const int th = conv_pack_geom2(kid, ek).th;
+  if (th <= 0) return false;
+  p.tiles_x = (p.w + 31) / 32;
+  p.tiles_y = (p.h + th - 1) / th;
+  return true;
+}
+int launch_conv(dd_handle_t h, int kid, int ek, ConvParams p, hipStream_t s, int slot) {
+  if (!conv_tiles(p, kid, ek)) return h->fail(DD_ERR_INVALID_ARG, "no fused convolution kernel for kernel id " + std::to_string(kid) + " in element kind " + std::to_string(ek));
+  DD_HIP(timed(h, slot, s, [&] { return launch_conv_igemm2(kid, ek, p, s); }));
+  return DD_OK;
 }
 
 int get_plan(dd_handle_t h, const PlanKey& key, Plan** out) {
@@ -170,7 +183,6 @@ int get_plan(dd_handle_t h, const PlanKey& key, Plan** out) {
   if (key.keep) DD_HIP(pl->xstash.alloc((size_t)(key.T > 0 ? key.T : 1) * px * LATENT_C * 4));
   const bool swin = h->variant == DD_VARIANT_SWIN;
   // Swin: the condition map is bilinearly upsampled to the latent size once per call and kept at that size
-  (void)swin;
   // (refined f16, Res denoiser: hoisted forward-only plans whose loop never reads the condition map, and whose once-per-image conv3(cond) reads an
   // explicit `cond` tensor in place (option "cond_direct"): the blocked fp32 buffer -- 219 MB at KITTI B = 4 -- is only allocated when a call needs
   // it: a non-direct stage_condition, or dd_condition's resident map)
@@ -183,7 +195,9 @@ int get_plan(dd_handle_t h, const PlanKey& key, Plan** out) {
   }
   if (key.hoist)   // conv3(cond) in accumulator-fragment order: whole (th x 32)-pixel tiles
   {
-    const int th = conv_pack_geom2(conv3h_kid(h, key), pl->ek).th;
+    PackGeom g3;
+    DD_TRY(pack_geom(h, conv3h_kid(h, key), pl->ek, &g3));
+    const int th = g3.th;
     DD_HIP(pl->ccond.alloc((size_t)key.B * ((key.h + th - 1) / th) * ((key.w + 31) / 32) * th * 32 * HID_C * 4));
     if (pl->ek == EK_F16R) {
       pl->wide = h->f16r_wide != 0; pl->c1 = h->f16r_c1 != 0; pl->p4 = h->f16r_p4 != 0;
@@ -250,8 +264,6 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
   const PlanKey& k = pl->key;
   ConvParams p{};
   p.B = k.B; p.h = k.h; p.w = k.w;
-  p.tiles_x = (k.w + 31) / 32;
-  p.tiles_y = (k.h + 7) / 8;
   p.ablate = h->ablate;
   // the loop's timesteps are the plan's own schedule: pass the value, not the address (clamped as clamp_t does on the device)
   if (tvec == pl->tsteps.as<long long>() && t_bstride == 0 && t_base >= 0 && t_base < (int)pl->tsteps_host.size())
@@ -262,27 +274,21 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
   // conv4 runs as the persistent streaming kernel of dd_thin.hip in the 2-byte modes (option "thin_stream", default on; the phase profiler
   // instruments the general kernel)
   const bool stream4 = h->thin_stream && (tk == EK_F16 || tk == EK_BF16) && !h->prof_buf && k.B <= h->thin_slots;
-  auto timed_launch = [&](int layer, const ConvParams& cp, int kid_as = -1) -> hipError_t {
-    const int kid = kid_as >= 0 ? kid_as : layer == 9 ? conv3h_kid(h, k) : layer;            // kernel id; times are booked under `layer`
-    auto launch = [&](ConvParams q) {
-      q.prof = (h->prof_buf && layer == h->prof_layer) ? h->prof_buf : nullptr;
-      q.tiles_y = (k.h + conv_pack_geom2(kid, ek).th - 1) / conv_pack_geom2(kid, ek).th;
-      if (layer == 4 && rf) { q.persist_slots = h->thin_slots; q.cadd_scale = static_cast<const float*>(pl->slot(pl->y3_scale, step)); return launch_conv4_stream(EK_F16, q, s, true, pl->wide, pl->p4); }
-      if (layer == 4 && stream4) { q.persist_slots = h->thin_slots; return launch_conv4_stream(tk, q, s); }
-      int lek = ek;
-      if (rf && (layer == 9 || layer == 7) && !pl->wide) lek = EK_F16;      // hand-over of y3 / the hoisted term as f16: the f16 mode's conv3 / 5x5 form
-      if (rf && layer == 1 && !pl->c1) lek = EK_F16;        // conv1 without the weight pair: the f16 mode's conv1
-      return launch_conv_igemm2(kid, lek, q, s);
-    };
-    if (!h->layer_timing) return launch(cp);
-    hipEvent_t a, b;
-    hipError_t e = hipEventCreate(&a); if (e != hipSuccess) return e;
-    e = hipEventCreate(&b); if (e != hipSuccess) return e;
-    (void)hipEventRecord(a, s);
-    e = launch(cp);
-    (void)hipEventRecord(b, s);
-    h->pending_ev.emplace_back(layer - 1, a, b);
-    return e;
+  // what is specific to the denoiser step: conv4 as the streaming kernel, the refined mode's kind substitutions, the profiler pointer
+  auto timed_launch = [&](int layer, ConvParams q, int kid_as = 0) -> int {
+    const int kid = kid_as ? kid_as : layer == KID_CONV3H ? conv3h_kid(h, k) : layer;            // kernel id; times are booked under `layer`
+    q.prof = (h->prof_buf && layer == h->prof_layer) ? h->prof_buf : nullptr;
+    if (layer == KID_CONV4 && (rf || stream4)) {
+      if (!conv_tiles(q, KID_CONV4, tk)) return h->fail(DD_ERR_INVALID_ARG, "conv4 has no packed geometry in this element kind");
+      q.persist_slots = h->thin_slots;
+      if (rf) q.cadd_scale = static_cast<const float*>(pl->slot(pl->y3_scale, step));
+      DD_HIP(timed(h, layer, s, [&] { return rf ? launch_conv4_stream(EK_F16, q, s, true, pl->wide, pl->p4) : launch_conv4_stream(tk, q, s); }));
+      return DD_OK;
+    }
+    int lek = ek;
+    if (rf && (layer == KID_CONV3H || layer == KID_SWIN_PRED) && !pl->wide) lek = EK_F16;      // hand-over of y3 / the hoisted term as f16: the f16 mode's conv3 / 5x5 form
+    if (rf && layer == KID_CONV1 && !pl->c1) lek = EK_F16;        // conv1 without the weight pair: the f16 mode's conv1
+    return launch_conv(h, kid, lek, q, s, layer);
   };
   // this step's activation buffers (per-step slots in the plans that keep them for the backward)
   void *y1_ = pl->slot(pl->y1, step), *y2_ = pl->slot(pl->y2, step), *y3_ = pl->slot(pl->y3, step), *y4_ = pl->slot(pl->y4, step);
@@ -294,19 +300,19 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
   p.stats_in = apply_update ? pl->stat_ptr(step - 1, 3) : nullptr;
   p.gn_gamma = h->L[3].gamma.as<float>(); p.gn_beta = h->L[3].beta.as<float>();
   p.y4 = y4_prev; p.xout = x_out; p.c1c2 = pl->c1c2.as<float>(); p.step = apply_update ? step : 0;
-  DD_HIP(timed_launch(1, p));
+  DD_TRY(timed_launch(KID_CONV1, p));
   // conv2: relu(gn1(y1)) -> y2
   p.in = y1_; p.wpack = h->L[1].wpack2[wk].p; p.bias = h->L[1].bias.as<float>(); p.out = y2_;
   p.stats_out = pl->stat_ptr(step, 1); p.stats_in = pl->stat_ptr(step, 0);
   p.gn_gamma = h->L[0].gamma.as<float>(); p.gn_beta = h->L[0].beta.as<float>();
-  DD_HIP(timed_launch(2, p));
+  DD_TRY(timed_launch(KID_CONV2, p));
   if (h->variant == DD_VARIANT_SWIN && k.hoist) {
     // hoisted form: pred.0(convB(convA(relu(gn2(y2))))) without the fuse convs' biases; the accumulators of pred.0 start at the per-image
     // term of enqueue_swin_hoist and its epilogue adds this step's E[t] rows
     p.in = y2_; p.wpack = h->LA.wpack2[wk].p; p.bias = h->zero_bias.as<float>(); p.out = sa_;
     p.stats_out = nullptr; p.stats_in = pl->stat_ptr(step, 1);
     p.gn_gamma = h->L[1].gamma.as<float>(); p.gn_beta = h->L[1].beta.as<float>();
-    DD_HIP(timed_launch(5, p, SWIN_CONVA_H));
+    DD_TRY(timed_launch(KID_SWIN_CONVA, p, SWIN_CONVA_H));
     p.stats_in = nullptr;
     p.cadd = pl->ccond.as<float>(); p.ttab = pl->ttab.as<float>() + (size_t)step * SWIN_TT_ROWS * HID_C;
     p.ttab_bstride = k.T > 0 ? 0 : SWIN_TT_ROWS * HID_C;
@@ -316,13 +322,13 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
       p.in = sa_; p.wpack = h->w5pack[wk].p; p.bias = h->L[2].bias.as<float>(); p.out = y3_;
       p.stats_out = pl->stat_ptr(step, 2); p.bcorr = pl->bcorr.as<float>();
       p.cadd_scale = pl->ccond_scale.as<float>(); p.out_scale = static_cast<float*>(pl->slot(pl->y3_scale, step));      // (EK_F16R form only)
-      DD_HIP(timed_launch(7, p, plan_big_tiles(h, k) ? (int)SWIN_PRED5B_H : (int)SWIN_PRED5_H));
+      DD_TRY(timed_launch(KID_SWIN_PRED, p, plan_big_tiles(h, k) ? SWIN_PRED5B_H : SWIN_PRED5_H));
     } else {
       p.in = sa_; p.wpack = h->LB.wpack2[wk].p; p.out = sf_;
-      DD_HIP(timed_launch(6, p));
+      DD_TRY(timed_launch(KID_SWIN_CONVB, p));
       p.in = sf_; p.wpack = h->L[2].wpack2[wk].p; p.bias = h->L[2].bias.as<float>(); p.out = y3_;
       p.stats_out = pl->stat_ptr(step, 2);
-      DD_HIP(timed_launch(7, p, SWIN_PRED_H));
+      DD_TRY(timed_launch(KID_SWIN_PRED, p, SWIN_PRED_H));
     }
   } else if (h->variant == DD_VARIANT_SWIN) {
     // upsample_fuse: convB(convA(relu(gn2(y2)) + up(cond) + E[t]))  then pred.0 on the raw result
@@ -330,13 +336,13 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
     p.stats_out = nullptr; p.stats_in = pl->stat_ptr(step, 1);
     p.gn_gamma = h->L[1].gamma.as<float>(); p.gn_beta = h->L[1].beta.as<float>();
     p.cond = pl->cond_ptr(); p.emb = h->emb.as<float>(); p.tvec = tvec; p.t_base = t_base; p.t_bstride = t_bstride;
-    DD_HIP(timed_launch(5, p));
+    DD_TRY(timed_launch(KID_SWIN_CONVA, p));
     p.in = sa_; p.wpack = h->LB.wpack2[wk].p; p.bias = h->LB.bias.as<float>(); p.out = sf_;
     p.stats_in = nullptr;
-    DD_HIP(timed_launch(6, p));
+    DD_TRY(timed_launch(KID_SWIN_CONVB, p));
     p.in = sf_; p.wpack = h->L[2].wpack2[wk].p; p.bias = h->L[2].bias.as<float>(); p.out = y3_;
     p.stats_out = pl->stat_ptr(step, 2);
-    DD_HIP(timed_launch(7, p));
+    DD_TRY(timed_launch(KID_SWIN_PRED, p));
   } else {
   // conv3: relu(gn2(y2)) + cond + E[t] -> y3   (hoisted form: conv3(relu(gn2(y2))) + [conv3(cond) + conv3(E[t])])
   p.in = y2_; p.wpack = h->L[2].wpack2[wk].p; p.bias = h->L[2].bias.as<float>(); p.out = y3_;
@@ -345,14 +351,14 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
   p.cond = pl->cond_ptr(); p.emb = h->emb.as<float>(); p.tvec = tvec; p.t_base = t_base; p.t_bstride = t_bstride;
   p.cadd = pl->ccond.as<float>(); p.etab = h->etab.as<float>();
   p.cadd_scale = pl->ccond_scale.as<float>(); p.out_scale = static_cast<float*>(pl->slot(pl->y3_scale, step));      // (EK_F16R forms only)
-  DD_HIP(timed_launch(k.hoist ? 9 : 3, p));
+  DD_TRY(timed_launch(k.hoist ? KID_CONV3H : KID_CONV3, p));
   p.cadd_scale = nullptr; p.out_scale = nullptr;
   }
   // conv4: relu(gn3(y3)) -> y4 (fp32)
   p.in = y3_; p.wpack = h->L[3].wpack2[rf ? WIMG_STACK : wimg_slot(tk)].p; p.bias = h->L[3].bias.as<float>(); p.out = y4_;
   p.stats_out = pl->stat_ptr(step, 3); p.stats_in = pl->stat_ptr(step, 2);
   p.gn_gamma = h->L[2].gamma.as<float>(); p.gn_beta = h->L[2].beta.as<float>();
-  DD_HIP(timed_launch(4, p));
+  DD_TRY(timed_launch(KID_CONV4, p));
   if (h->debug_sync) DD_HIP(hipStreamSynchronize(s));
   return DD_OK;
 }
@@ -389,23 +395,17 @@ int enqueue_cond_conv(dd_handle_t h, Plan* pl, hipStream_t s, const float* nchw)
   const PlanKey& k = pl->key;
   ConvParams p{};
   p.B = k.B; p.h = k.h; p.w = k.w;
-  p.tiles_x = (k.w + 31) / 32;
-  p.ablate = 0;
   if (pl->ek == EK_F16R) {
     // refined f16: the split-f16 layer 8 on the fp32 condition map (the term is exact to ~22 bits), fp32 in the order of 8x32 tiles; then into
     // the order / element type the loop's conv3 reads (block-scaled int16 or f16 quads, 8x32 or 16x32 tiles)
-    p.tiles_y = (k.h + 7) / 8;
     p.in = nchw ? static_cast<const void*>(nchw) : pl->cond_ptr(); p.wpack = h->L[2].wpack2[WIMG_SPLIT].p; p.bias = h->zero_bias.as<float>();
     p.out = pl->ccond_raw.p;
-    DD_HIP(launch_conv_igemm2(nchw ? CONV3C_NCHW : 8, EK_F16S, p, s));
+    DD_TRY(launch_conv(h, nchw ? CONV3C_NCHW : KID_CONV3C, EK_F16S, p, s));
     DD_HIP(launch_cadd_reformat(pl->ccond_raw.as<float>(), pl->ccond.p, pl->ccond_scale.as<float>(), k.B, k.h, k.w, plan_big_tiles(h, k) ? 1 : 0, pl->wide ? 2 : 1, s));
     return DD_OK;
   }
-  const int kid = conv3c_kid(h, k);
-  p.tiles_y = (k.h + conv_pack_geom2(kid, pl->ek).th - 1) / conv_pack_geom2(kid, pl->ek).th;
   p.in = pl->cond_ptr(); p.wpack = h->L[2].wpack2[wimg_slot(thin_kind(pl->ek))].p; p.bias = h->zero_bias.as<float>(); p.out = pl->ccond.p;
-  DD_HIP(launch_conv_igemm2(kid, pl->ek, p, s));
-  return DD_OK;
+  return launch_conv(h, conv3c_kid(h, k), pl->ek, p, s);
 }
 
 
@@ -422,8 +422,9 @@ int ensure_swin_w5(dd_handle_t h, hipStream_t s) {
   for (int wi = 0; wi < NUM_WIMG; ++wi) {
     if (wi == WIMG_STACK) continue;
     const int ekk = wimg_kind(wi);
-    const PackGeom g5 = conv_pack_geom2(SWIN_PRED5_H, ekk);
-    int rc = ensure_bytes(h, h->w5pack[wi], pack_weights_bytes(g5, ekk)); if (rc) return rc;
+    PackGeom g5;
+    int rc = pack_geom(h, SWIN_PRED5_H, ekk, &g5); if (rc) return rc;
+    rc = ensure_bytes(h, h->w5pack[wi], pack_weights_bytes(g5, ekk)); if (rc) return rc;
     DD_HIP(launch_pack_weights(h->w5_oihw.as<float>(), h->w5pack[wi].p, g5, ekk, true, false, s));
   }
   h->w5_weights = h->weights_serial;
@@ -444,31 +445,25 @@ int enqueue_swin_hoist(dd_handle_t h, Plan* pl, hipStream_t s) {
   if (pl->bcorr.p) { int rc = ensure_swin_w5(h, s); if (rc) return rc; }
   ConvParams p{};
   p.B = k.B; p.h = k.h; p.w = k.w;
-  p.tiles_x = (k.w + 31) / 32;
   if (pl->ek == EK_F16R) {
     // refined f16: the whole once-per-image chain on split operands (EK_F16S kernels, fp32 tensors: the upsampled condition map is fp32 in this
     // mode), its result in the order of 8x32 tiles, then reformatted into what the loop's 5x5 kernel reads (as the Res variant's conv3(cond))
-    p.tiles_y = (k.h + 7) / 8;
     p.in = pl->cond_ptr(); p.wpack = h->LA.wpack2[WIMG_SPLIT].p; p.bias = h->LA.bias.as<float>(); p.out = pl->sa.p;
-    DD_HIP(launch_conv_igemm2(6, EK_F16S, p, s));
+    DD_TRY(launch_conv(h, KID_SWIN_CONVB, EK_F16S, p, s));
     p.in = pl->sa.p; p.wpack = h->LB.wpack2[WIMG_SPLIT].p; p.bias = h->LB.bias.as<float>(); p.out = pl->sf.p;
-    DD_HIP(launch_conv_igemm2(6, EK_F16S, p, s));
+    DD_TRY(launch_conv(h, KID_SWIN_CONVB, EK_F16S, p, s));
     p.in = pl->sf.p; p.wpack = h->L[2].wpack2[WIMG_SPLIT].p; p.bias = h->zero_bias.as<float>(); p.out = pl->ccond_raw.p;
-    DD_HIP(launch_conv_igemm2(8, EK_F16S, p, s));
+    DD_TRY(launch_conv(h, KID_CONV3C, EK_F16S, p, s));
     DD_HIP(launch_cadd_reformat(pl->ccond_raw.as<float>(), pl->ccond.p, pl->ccond_scale.as<float>(), k.B, k.h, k.w, plan_big_tiles(h, k) ? 1 : 0, pl->wide ? 2 : 1, s));
     return DD_OK;
   }
   const int tk = thin_kind(pl->ek);           // once per image: f16 kernels in the bf16 mode, as the Res variant's conv3(cond)
-  p.tiles_y = (k.h + conv_pack_geom2(6, tk).th - 1) / conv_pack_geom2(6, tk).th;
   p.in = pl->cond_ptr(); p.wpack = h->LA.wpack2[wimg_slot(tk)].p; p.bias = h->LA.bias.as<float>(); p.out = pl->sa.p;
-  DD_HIP(launch_conv_igemm2(6, tk, p, s));
+  DD_TRY(launch_conv(h, KID_SWIN_CONVB, tk, p, s));
   p.in = pl->sa.p; p.wpack = h->LB.wpack2[wimg_slot(tk)].p; p.bias = h->LB.bias.as<float>(); p.out = pl->sf.p;
-  DD_HIP(launch_conv_igemm2(6, tk, p, s));
-  const int kid8 = conv3c_kid(h, k);          // (16x32 tiles when the loop's pred.0 kernel runs on them: the two agree on the fragment order)
-  p.tiles_y = (k.h + conv_pack_geom2(kid8, pl->ek).th - 1) / conv_pack_geom2(kid8, pl->ek).th;
+  DD_TRY(launch_conv(h, KID_SWIN_CONVB, tk, p, s));
   p.in = pl->sf.p; p.wpack = h->L[2].wpack2[wimg_slot(tk)].p; p.bias = h->zero_bias.as<float>(); p.out = pl->ccond.p;
-  DD_HIP(launch_conv_igemm2(kid8, pl->ek, p, s));
-  return DD_OK;
+  return launch_conv(h, conv3c_kid(h, k), pl->ek, p, s);      // (16x32 tiles when the loop's pred.0 kernel runs on them: the two agree on the fragment order)
 }
 
 // Bring the condition map into the plan's (shared) buffer: convert the caller's NCHW fp32 tensor, or -- cond == NULL --

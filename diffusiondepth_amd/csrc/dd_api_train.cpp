@@ -191,13 +191,10 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
     if (naive) {
       DD_HIP(launch_naive_conv3x3(pl->gY.as<float>(), h->L[l].wT_oihw.as<float>(), nullptr, pl->gA.as<float>(), B, lat_h, lat_w, C, CI, s));
     } else {
-      const int layer = 23 - l;
       ConvParams q{};
       q.B = B; q.h = lat_h; q.w = lat_w;
-      q.tiles_x = (lat_w + 31) / 32;
-      q.tiles_y = (lat_h + conv_pack_geom2(layer, ek).th - 1) / conv_pack_geom2(layer, ek).th;
       q.in = pl->gY.p; q.wpack = h->L[l].wpackT[ek].p; q.bias = h->zero_bias.as<float>(); q.out = pl->gA.p;
-      DD_HIP(launch_conv_igemm2(layer, ek, q, s));          // data gradients: plain kinds (bf16 in the mode EK_BF16M)
+      DD_TRY(launch_conv(h, kid_dgrad(l), ek, q, s));          // data gradients: plain kinds (bf16 in the mode EK_BF16M)
     }
     rc = chk("weight gradient (dw, accumulated)", l, dw, (long long)C * CI * 9, 0); if (rc) return rc;
     rc = chk("dLoss/d(input) out of the data-gradient convolution (gA)", l, pl->gA.p, (long long)B * CI * HW, (naive || l == 0) ? 0 : kk); if (rc) return rc;
@@ -223,10 +220,8 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
         }
         ConvParams q{};
         q.B = B; q.h = lat_h; q.w = lat_w;
-        q.tiles_x = (lat_w + 31) / 32;
-        q.tiles_y = (lat_h + conv_pack_geom2(6, ek).th - 1) / conv_pack_geom2(6, ek).th;
         q.in = gbuf[i]; q.wpack = FL[i]->wpackT[ek].p; q.bias = h->zero_bias.as<float>(); q.out = gbuf[i + 1];
-        DD_HIP(launch_conv_igemm2(6, ek, q, s));
+        DD_TRY(launch_conv(h, KID_SWIN_CONVB, ek, q, s));      // (convB's kernel: 256 -> 256 on a raw input, here on the transposed weights)
       }
     }
     if (l == 2) {

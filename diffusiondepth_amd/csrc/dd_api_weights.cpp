@@ -216,6 +216,24 @@ int pull_device_weights_to_host(dd_handle_t h, hipStream_t s) {
   return DD_OK;
 }
 
+// The packed-image geometry of kernel (kid, ek).  A pair no kernel runs (conv_pack_geom2's all-zero answer: a mistyped id, a kind the form does
+// not exist in) fails the call here -- it must not travel on as a zero-sized image, nor on pack_conv_weights' "does not fit the split image" signal.
+int pack_geom(dd_handle_t h, int kid, int ek, PackGeom* g) {
+  *g = conv_pack_geom2(kid, ek);
+  if (g->cout == 0) return h->fail(DD_ERR_INVALID_ARG, "no fused convolution kernel, hence no packed weight image, for kernel id " + std::to_string(kid) + " in element kind " + std::to_string(ek));
+  return DD_OK;
+}
+// Host route: one weight tensor into the packed image of kernel (kid, ek), uploaded to dst; *fits is cleared when a weight does not fit the split-f16 image
+static int pack_upload(dd_handle_t h, const float* w, int kid, int ek, DevBuf& dst, hipStream_t s, bool* fits = nullptr) {
+  PackGeom g;
+  DD_TRY(pack_geom(h, kid, ek, &g));
+  std::vector<uint8_t> packed;
+  if (!pack_conv_weights(w, g, ek, true, packed) && fits) *fits = false;
+  DD_TRY(upload(h, dst, packed.data(), packed.size(), s));
+  DD_HIP(hipStreamSynchronize(s));     // `packed` is a temporary
+  return DD_OK;
+}
+
 int ensure_bytes(dd_handle_t h, DevBuf& dst, size_t bytes) {
   if (dst.bytes < bytes || !dst.p) DD_HIP(dst.alloc(bytes));
   return DD_OK;
@@ -227,11 +245,12 @@ int pack_conv_layer_device(dd_handle_t h, ConvLayer& L, const float* w, int fwd_
   for (int wi = 0; wi < NUM_WIMG; ++wi) {
     if (!wimg_has(wi, fwd_layer)) continue;
     const int ek = wimg_kind(wi);
-    const PackGeom g2 = conv_pack_geom2(fwd_layer, ek);
-    int rc = ensure_bytes(h, L.wpack2[wi], pack_weights_bytes(g2, ek)); if (rc) return rc;
+    PackGeom g2, gt;
+    int rc = pack_geom(h, fwd_layer, ek, &g2); if (rc) return rc;
+    rc = ensure_bytes(h, L.wpack2[wi], pack_weights_bytes(g2, ek)); if (rc) return rc;
     DD_HIP(launch_pack_weights(w, L.wpack2[wi].p, g2, ek, true, false, s));
     if (wi == WIMG_SPLIT || wi == WIMG_STACK) continue;           // the split / refined f16 modes are forward only
-    const PackGeom gt = conv_pack_geom2(dgrad_layer, ek);
+    rc = pack_geom(h, dgrad_layer, ek, &gt); if (rc) return rc;
     rc = ensure_bytes(h, L.wpackT[ek], pack_weights_bytes(gt, ek)); if (rc) return rc;
     DD_HIP(launch_pack_weights(w, L.wpackT[ek].p, gt, ek, true, true, s));
   }
@@ -259,7 +278,7 @@ int commit_model_from_device(dd_handle_t h, hipStream_t s) {
   for (int l = 0; l < 4; ++l) {
     ConvLayer& L = h->L[l];
     L.cin = kCins[l]; L.cout = kCouts[l];
-    int rc = pack_conv_layer_device(h, L, D(std::string(kConvNames[l]) + ".weight"), l + 1, 23 - l, true, s); if (rc) return rc;
+    int rc = pack_conv_layer_device(h, L, D(std::string(kConvNames[l]) + ".weight"), kid_denoiser(l), kid_dgrad(l), true, s); if (rc) return rc;
     rc = copy_small(L.bias, std::string(kConvNames[l]) + ".bias", 32); if (rc) return rc;
     rc = copy_small(L.gamma, std::string(kGnNames[l]) + ".weight", 0); if (rc) return rc;
     rc = copy_small(L.beta, std::string(kGnNames[l]) + ".bias", 0); if (rc) return rc;
@@ -270,7 +289,7 @@ int commit_model_from_device(dd_handle_t h, hipStream_t s) {
     for (int i = 0; i < 2; ++i) {
       ConvLayer& L = *Ls[i];
       L.cin = COND_C; L.cout = COND_C;
-      int rc = pack_conv_layer_device(h, L, D(std::string(names[i]) + ".weight"), 5 + i, 6, false, s); if (rc) return rc;
+      int rc = pack_conv_layer_device(h, L, D(std::string(names[i]) + ".weight"), kid_swin_fuse(i), KID_SWIN_CONVB, false, s); if (rc) return rc;
       rc = ensure_bytes(h, L.w_oihw, (size_t)COND_C * COND_C * 9 * 4); if (rc) return rc;      // fp32 OIHW: the hoisted form's E[t] tables / 5x5 composition
       DD_HIP(hipMemcpyAsync(L.w_oihw.p, D(std::string(names[i]) + ".weight"), (size_t)COND_C * COND_C * 9 * 4, hipMemcpyDeviceToDevice, s));
       rc = copy_small(L.bias, std::string(names[i]) + ".bias", 0); if (rc) return rc;
@@ -353,12 +372,8 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
     const std::vector<float>& w = h->host_w[std::string(conv_names[l]) + ".weight"];
     const std::vector<float>& b = h->host_w[std::string(conv_names[l]) + ".bias"];
     for (int wi = 0; wi < NUM_WIMG; ++wi) {
-      if (!wimg_has(wi, l + 1)) continue;
-      std::vector<uint8_t> packed;
-      if (!pack_conv_weights(w.data(), conv_pack_geom2(l + 1, wimg_kind(wi)), wimg_kind(wi), true, packed)) split_fits = false;
-      int rc = upload(h, L.wpack2[wi], packed.data(), packed.size(), s);
-      if (rc) return rc;
-      DD_HIP(hipStreamSynchronize(s));     // `packed` is a temporary
+      if (!wimg_has(wi, kid_denoiser(l))) continue;
+      DD_TRY(pack_upload(h, w.data(), kid_denoiser(l), wimg_kind(wi), L.wpack2[wi], s, &split_fits));
     }
     std::vector<float> bpad(std::max(32, L.cout), 0.f);
     std::copy(b.begin(), b.end(), bpad.begin());
@@ -372,12 +387,7 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
           for (int k = 0; k < 9; ++k) wt[((size_t)ci * L.cout + co) * 9 + (8 - k)] = w[((size_t)co * L.cin + ci) * 9 + k];
       rc = upload(h, L.wT_oihw, wt.data(), wt.size() * 4, s); if (rc) return rc;
       DD_HIP(hipStreamSynchronize(s));
-      for (int ek = 0; ek < NUM_EK; ++ek) {
-        std::vector<uint8_t> packed;
-        pack_conv_weights(wt.data(), conv_pack_geom2(23 - l, ek), ek, true, packed);
-        rc = upload(h, L.wpackT[ek], packed.data(), packed.size(), s); if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
-      }
+      for (int ek = 0; ek < NUM_EK; ++ek) DD_TRY(pack_upload(h, wt.data(), kid_dgrad(l), ek, L.wpackT[ek], s));
     }
     const std::vector<float>& gg = h->host_w[std::string(gn_names[l]) + ".weight"];
     const std::vector<float>& gb = h->host_w[std::string(gn_names[l]) + ".bias"];
@@ -394,12 +404,8 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
       const std::vector<float>& w = h->host_w[std::string(names[i]) + ".weight"];
       const std::vector<float>& b = h->host_w[std::string(names[i]) + ".bias"];
       for (int wi = 0; wi < NUM_WIMG; ++wi) {
-        if (!wimg_has(wi, 5 + i)) continue;
-        std::vector<uint8_t> packed;
-        if (!pack_conv_weights(w.data(), conv_pack_geom2(5 + i, wimg_kind(wi)), wimg_kind(wi), true, packed)) split_fits = false;
-        int rc = upload(h, L.wpack2[wi], packed.data(), packed.size(), s);
-        if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
+        if (!wimg_has(wi, kid_swin_fuse(i))) continue;
+        DD_TRY(pack_upload(h, w.data(), kid_swin_fuse(i), wimg_kind(wi), L.wpack2[wi], s, &split_fits));
       }
       int rc = upload(h, L.bias, b.data(), b.size() * 4, s); if (rc) return rc;
       rc = upload(h, L.w_oihw, w.data(), w.size() * 4, s); if (rc) return rc;       // fp32 OIHW: the hoisted form's E[t] tables (swin_ttab)
@@ -409,12 +415,7 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
       for (int co = 0; co < COND_C; ++co)
         for (int ci = 0; ci < COND_C; ++ci)
           for (int k = 0; k < 9; ++k) wt[((size_t)ci * COND_C + co) * 9 + (8 - k)] = w[((size_t)co * COND_C + ci) * 9 + k];
-      for (int ek = 0; ek < NUM_EK; ++ek) {
-        std::vector<uint8_t> packed;
-        pack_conv_weights(wt.data(), conv_pack_geom2(6, ek), ek, true, packed);
-        rc = upload(h, L.wpackT[ek], packed.data(), packed.size(), s); if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
-      }
+      for (int ek = 0; ek < NUM_EK; ++ek) DD_TRY(pack_upload(h, wt.data(), KID_SWIN_CONVB, ek, L.wpackT[ek], s));
     }
   }
   if (do_model) {
@@ -453,12 +454,8 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
       std::vector<float> w((size_t)COND_C * per_pad, 0.f);
       for (int co = 0; co < COND_C; ++co)
         for (size_t k = 0; k < per; ++k) w[co * per_pad + k] = (float)((double)w0[co * per + k] * sc[co]);
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) {        // fp32, bf16, f16 and the split-f16 image (the split / refined modes' pyramid)
-        std::vector<uint8_t> packed;
-        if (!pack_conv_weights(w.data(), conv_pack_geom2(fpn_lat_layer(h->variant, h->fpn_pyramid, i), wimg_kind(wi)), wimg_kind(wi), true, packed)) fpn_fits = false;
-        int rc = upload(h, h->fpn_lat_w[i][wi], packed.data(), packed.size(), s); if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
-      }
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi)        // fp32, bf16, f16 and the split-f16 image (the split / refined modes' pyramid)
+        DD_TRY(pack_upload(h, w.data(), kid_fpn_lateral(pyramid_of(h->variant, h->fpn_pyramid), i), wimg_kind(wi), h->fpn_lat_w[i][wi], s, &fpn_fits));
       int rc = upload(h, h->fpn_lat_b[i], sh.data(), sh.size() * 4, s); if (rc) return rc;
       DD_HIP(hipStreamSynchronize(s));
     }
@@ -475,12 +472,7 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
           for (int ci = 0; ci < COND_C; ++ci)
             w[((size_t)par * COND_C + co) * COND_C + ci] = (float)((double)wt[((size_t)ci * COND_C + co) * 4 + par] * sc[co]);
         }
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) {
-        std::vector<uint8_t> packed;
-        if (!pack_conv_weights(w.data(), conv_pack_geom2(14, wimg_kind(wi)), wimg_kind(wi), true, packed)) fpn_fits = false;
-        int rc = upload(h, h->fpn_up_w[j][wi], packed.data(), packed.size(), s); if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
-      }
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_TRY(pack_upload(h, w.data(), KID_FPN_UP, wimg_kind(wi), h->fpn_up_w[j][wi], s, &fpn_fits));
       int rc = upload(h, h->fpn_up_b[j], b4.data(), b4.size() * 4, s); if (rc) return rc;
       DD_HIP(hipStreamSynchronize(s));
     }
@@ -497,7 +489,8 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
       const auto &g = h->host_w[c.name + ".bn.weight"], &b = h->host_w[c.name + ".bn.bias"], &m = h->host_w[c.name + ".bn.running_mean"],
                  &v = h->host_w[c.name + ".bn.running_var"];
       const std::vector<float>& w0 = h->host_w[c.name + ".conv.weight"];
-      const PackGeom pg = conv_pack_geom2(c.layer, EK_F32);
+      PackGeom pg;
+      DD_TRY(pack_geom(h, c.layer, EK_F32, &pg));
       const int kk = c.ks * c.ks, cin_k = pg.cin, cout_k = pg.cout;
       std::vector<float> w((size_t)cout_k * cin_k * kk, 0.f), sh((size_t)pg.cout_pad, 0.f);
       for (int co = 0; co < c.cout; ++co) {
@@ -505,18 +498,13 @@ int dd_commit_weights(dd_handle_t h, void* stream) {
         sh[co] = (float)((double)b[co] - (double)m[co] * sc);
         for (int ci = 0; ci < c.cin; ++ci) {
           int cik = ci;
-          if (c.kind == 2 && c.level > 0 && ci >= c.C) cik = ci - c.C + c.Ck;          // [lateral | projection]: the projection part starts at Ck
+          if (c.kind == NECK_FUSION && c.level > 0 && ci >= c.C) cik = ci - c.C + c.Ck;          // [lateral | projection]: the projection part starts at Ck
           for (int k = 0; k < kk; ++k)
             w[((size_t)co * cin_k + cik) * kk + k] = (float)((double)w0[((size_t)co * c.cin + ci) * kk + k] * sc);
         }
       }
-      const int slot = c.layer - neck_base(h->fpn_pyramid);
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) {
-        std::vector<uint8_t> packed;
-        if (!pack_conv_weights(w.data(), conv_pack_geom2(c.layer, wimg_kind(wi)), wimg_kind(wi), true, packed)) neck_fits = false;
-        int rc = upload(h, h->neck_w[slot][wi], packed.data(), packed.size(), s); if (rc) return rc;
-        DD_HIP(hipStreamSynchronize(s));
-      }
+      const int slot = 4 * c.kind + c.level;
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_TRY(pack_upload(h, w.data(), c.layer, wimg_kind(wi), h->neck_w[slot][wi], s, &neck_fits));
       int rc = upload(h, h->neck_b[slot], sh.data(), sh.size() * 4, s); if (rc) return rc;
       DD_HIP(hipStreamSynchronize(s));
     }

@@ -804,7 +804,7 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
           const int lg = (C::COUT == COND_C) ? (n >> 1) : (C::COUT == HID_C) ? (2 * n + (q >> 1)) : q;
           ls[lg] += s; lq[lg] += sq;
         }
-        if constexpr (C::LAYER == 8) {
+        if constexpr (C::LAYER == KID_CONV3C) {
           // hoisted condition term: fp32, accumulator-fragment order [tile][wave][n][m][q][lane] (read back by layer 9 only)
           const size_t fi = ((((size_t)e_tile * C::WAVES + wave) * C::WN + n) * C::WM + m) * 256 + q * 64 + lane;
           if constexpr (C::CADD16) reinterpret_cast<uint2*>(p.out)[fi] = make_uint2(pack2<EK_F16>(v[0], v[1]), pack2<EK_F16>(v[2], v[3]));
@@ -902,238 +902,50 @@ static hipError_t launch_one2(const ConvParams& p, hipStream_t s) {
   hipLaunchKernelGGL(conv_igemm2_kernel<C>, grid, dim3(C::THREADS), C::SMEM_BYTES, s, p);
   return hipGetLastError();
 }
-template <int EK>
-static hipError_t launch_layer2(int layer, const ConvParams& p, hipStream_t s) {
-  switch (layer) {
-    case 1: return launch_one2<EK, 1>(p, s);
-    case 2: return launch_one2<EK, 2>(p, s);
-    case 3: return launch_one2<EK, 3>(p, s);
-    case 4: return launch_one2<EK, 4>(p, s);
-    case 5: return launch_one2<EK, 5>(p, s);
-    case 6: return launch_one2<EK, 6>(p, s);
-    case 7: return launch_one2<EK, 7>(p, s);
-    case 8: return launch_one2<EK, 8>(p, s);
-    case 9: return launch_one2<EK, 9>(p, s);
-    case 10: return launch_one2<EK, 10>(p, s);
-    case 11: return launch_one2<EK, 11>(p, s);
-    case 12: return launch_one2<EK, 12>(p, s);
-    case 13: return launch_one2<EK, 13>(p, s);
-    case 14: return launch_one2<EK, 14>(p, s);
-    case 15: return launch_one2<EK, 15>(p, s);
-    case 16: return launch_one2<EK, 16>(p, s);
-    case 17: return launch_one2<EK, 17>(p, s);
-    case 18: return launch_one2<EK, 18>(p, s);
-    case 20: return launch_one2<EK, 20>(p, s);
-    case 21: return launch_one2<EK, 21>(p, s);
-    case 22: return launch_one2<EK, 22>(p, s);
-    case 23: return launch_one2<EK, 23>(p, s);
-    case 24: return launch_one2<EK, 24>(p, s);
-    case 25: return launch_one2<EK, 25>(p, s);
-    case 26: return launch_one2<EK, 26>(p, s);
-    case 30: return launch_one2<EK, 30>(p, s);
-    case 31: return launch_one2<EK, 31>(p, s);
-    case 32: return launch_one2<EK, 32>(p, s);
-    case 33: return launch_one2<EK, 33>(p, s);
-    case 34: return launch_one2<EK, 34>(p, s);
-    case 35: return launch_one2<EK, 35>(p, s);
-    case 36: return launch_one2<EK, 36>(p, s);
-    case 37: return launch_one2<EK, 37>(p, s);
-    case 38: return launch_one2<EK, 38>(p, s);
-    case 39: return launch_one2<EK, 39>(p, s);
-    case 40: return launch_one2<EK, 40>(p, s);
-    case 41: return launch_one2<EK, 41>(p, s);
-    case BIG_CONV3C: if constexpr (EK != EK_F32) return launch_one2<EK, BIG_CONV3C>(p, s); else return hipErrorInvalidValue;
-    case BIG_CONV3H: if constexpr (EK != EK_F32) return launch_one2<EK, BIG_CONV3H>(p, s); else return hipErrorInvalidValue;
-    case ONE_CONV3H: if constexpr (EK == EK_F16) return launch_one2<EK, ONE_CONV3H>(p, s); else return launch_one2<EK, 9>(p, s);      // (instantiated for the kinds the denoiser's modes run)
-    case SWIN_CONVA_H: return launch_one2<EK, SWIN_CONVA_H>(p, s);
-    case SWIN_PRED_H: return launch_one2<EK, SWIN_PRED_H>(p, s);
-    case SWIN_PRED5_H: return launch_one2<EK, SWIN_PRED5_H>(p, s);
-    case SWIN_PRED5B_H: if constexpr (EK != EK_F32) return launch_one2<EK, SWIN_PRED5B_H>(p, s); else return hipErrorInvalidValue;
-    case 54: return launch_one2<EK, 54>(p, s);
-    case 55: return launch_one2<EK, 55>(p, s);
-    case 56: return launch_one2<EK, 56>(p, s);
-    case 57: return launch_one2<EK, 57>(p, s);
-    case 58: return launch_one2<EK, 58>(p, s);
-    case 59: return launch_one2<EK, 59>(p, s);
-    case 60: return launch_one2<EK, 60>(p, s);
-    case 61: return launch_one2<EK, 61>(p, s);
-    case 62: return launch_one2<EK, 62>(p, s);
-    case 63: return launch_one2<EK, 63>(p, s);
-    case 64: return launch_one2<EK, 64>(p, s);
-    case 65: return launch_one2<EK, 65>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-// EK_BF16M (bf16 operands, f16 storage; dd_kernels.h): the layers that change kind have their own instantiations, the thin / once-per-
-// image layers run as f16 kernels, everything else (Swin convB, inner FPN layers, data gradients) as bf16 kernels.
-static hipError_t launch_layer2_mixed(int layer, const ConvParams& p, hipStream_t s) {
-  switch (layer) {
-    case 1: case 4: case 8: return launch_layer2<EK_F16>(layer, p, s);
-    case 2: return launch_one2<EK_BF16M, 2>(p, s);
-    case 3: return launch_one2<EK_BF16M, 3>(p, s);
-    case 5: return launch_one2<EK_BF16M, 5>(p, s);
-    case 7: return launch_one2<EK_BF16M, 7>(p, s);
-    case 9: return launch_one2<EK_BF16M, 9>(p, s);
-    case BIG_CONV3C: return launch_one2<EK_F16, BIG_CONV3C>(p, s);          // (the once-per-image conv3(cond) is an f16 kernel in this mode)
-    case BIG_CONV3H: return launch_one2<EK_BF16M, BIG_CONV3H>(p, s);
-    case ONE_CONV3H: return launch_one2<EK_BF16M, ONE_CONV3H>(p, s);
-    case SWIN_CONVA_H: return launch_one2<EK_BF16M, SWIN_CONVA_H>(p, s);
-    case SWIN_PRED_H: return launch_one2<EK_BF16M, SWIN_PRED_H>(p, s);
-    case SWIN_PRED5_H: return launch_one2<EK_BF16M, SWIN_PRED5_H>(p, s);
-    case SWIN_PRED5B_H: return launch_one2<EK_BF16M, SWIN_PRED5B_H>(p, s);
-    case 10: return launch_one2<EK_BF16M, 10>(p, s);
-    case 15: return launch_one2<EK_BF16M, 15>(p, s);
-    case 24: return launch_one2<EK_BF16M, 24>(p, s);
-    default: return launch_layer2<EK_BF16>(layer, p, s);
-  }
-}
-// EK_F16S (split f16): the denoiser's layers and the once-per-image condition layers (FPN, HAHI neck)
-static hipError_t launch_layer2_split(int layer, const ConvParams& p, hipStream_t s) {
-  switch (layer) {
-#define DD_SPLIT_CASE(L) case L: return launch_one2<EK_F16S, L>(p, s);
-    DD_SPLIT_CASE(10) DD_SPLIT_CASE(11) DD_SPLIT_CASE(12) DD_SPLIT_CASE(13) DD_SPLIT_CASE(14) DD_SPLIT_CASE(15) DD_SPLIT_CASE(16) DD_SPLIT_CASE(17) DD_SPLIT_CASE(18)
-    DD_SPLIT_CASE(24) DD_SPLIT_CASE(25) DD_SPLIT_CASE(26)
-    DD_SPLIT_CASE(30) DD_SPLIT_CASE(31) DD_SPLIT_CASE(32) DD_SPLIT_CASE(33) DD_SPLIT_CASE(34) DD_SPLIT_CASE(35) DD_SPLIT_CASE(36) DD_SPLIT_CASE(37) DD_SPLIT_CASE(38) DD_SPLIT_CASE(39) DD_SPLIT_CASE(40) DD_SPLIT_CASE(41)
-    DD_SPLIT_CASE(54) DD_SPLIT_CASE(55) DD_SPLIT_CASE(56) DD_SPLIT_CASE(57) DD_SPLIT_CASE(58) DD_SPLIT_CASE(59) DD_SPLIT_CASE(60) DD_SPLIT_CASE(61) DD_SPLIT_CASE(62) DD_SPLIT_CASE(63) DD_SPLIT_CASE(64) DD_SPLIT_CASE(65)
-#undef DD_SPLIT_CASE
-    case 1: return launch_one2<EK_F16S, 1>(p, s);
-    case 2: return launch_one2<EK_F16S, 2>(p, s);
-    case 3: return launch_one2<EK_F16S, 3>(p, s);
-    case 4: return launch_one2<EK_F16S, 4>(p, s);
-    case 5: return launch_one2<EK_F16S, 5>(p, s);
-    case 6: return launch_one2<EK_F16S, 6>(p, s);
-    case 7: return launch_one2<EK_F16S, 7>(p, s);
-    case 8: return launch_one2<EK_F16S, 8>(p, s);
-    case 9: case ONE_CONV3H: return launch_one2<EK_F16S, 9>(p, s);
-    case CONV3C_NCHW: return launch_one2<EK_F16S, CONV3C_NCHW>(p, s);
-    case SWIN_CONVA_H: return launch_one2<EK_F16S, SWIN_CONVA_H>(p, s);
-    case SWIN_PRED5_H: return launch_one2<EK_F16S, SWIN_PRED5_H>(p, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-// EK_F16R (refined f16): conv1 and the hoisted conv3 have their own instantiations; everything else is the f16 mode's kernel (the split-f16
-// layer 8 and the stacked conv4 are launched by dd_api.cpp under their own kinds / launchers)
-static hipError_t launch_layer2_refined(int layer, const ConvParams& p, hipStream_t s) {
-  switch (layer) {
-    case 1: return launch_one2<EK_F16R, 1>(p, s);
-    case 9: return launch_one2<EK_F16R, 9>(p, s);
-    case BIG_CONV3H: return launch_one2<EK_F16R, BIG_CONV3H>(p, s);
-    case ONE_CONV3H: return launch_one2<EK_F16R, ONE_CONV3H>(p, s);
-    case SWIN_PRED5_H: return launch_one2<EK_F16R, SWIN_PRED5_H>(p, s);
-    case SWIN_PRED5B_H: return launch_one2<EK_F16R, SWIN_PRED5B_H>(p, s);
-    default: return launch_layer2<EK_F16>(layer, p, s);
-  }
-}
-hipError_t launch_conv_igemm2(int layer, int ek, const ConvParams& p, hipStream_t s) {
+// ---- dispatch: generated from the id list and the routing rule of dd_kernel_ids.h --------------------------------------------------------
+// op.run<EK, ID>() for the requested (id, kind) when the id is listed and the kind exists, else op.none(); what run does with a pair that
+// kid_route leaves without a kernel is the op's business (both ops below answer with their none())
+template <int ID, class Op> static auto for_kind(int ek, Op op) {
   switch (ek) {
-    case EK_F16R: return launch_layer2_refined(layer, p, s);
-    case EK_F16S: return launch_layer2_split(layer, p, s);
-    case EK_F32: return launch_layer2<EK_F32>(layer, p, s);
-    case EK_BF16: return launch_layer2<EK_BF16>(layer, p, s);
-    case EK_F16: return launch_layer2<EK_F16>(layer, p, s);
-    case EK_BF16M: return launch_layer2_mixed(layer, p, s);
-    default: return hipErrorInvalidValue;
+    case EK_F32: return op.template run<EK_F32, ID>();
+    case EK_BF16: return op.template run<EK_BF16, ID>();
+    case EK_F16: return op.template run<EK_F16, ID>();
+    case EK_BF16M: return op.template run<EK_BF16M, ID>();
+    case EK_F16S: return op.template run<EK_F16S, ID>();
+    case EK_F16R: return op.template run<EK_F16R, ID>();
+    default: return op.none();
   }
 }
+template <class Op> static auto for_kernel_id(int id, int ek, Op op) {
+  switch (id) {
+#define DD_KID_CASE(K) case K: return for_kind<K>(ek, op);
+    DD_KERNEL_IDS(DD_KID_CASE)
+#undef DD_KID_CASE
+    default: return op.none();
+  }
+}
+struct LaunchOp {
+  const ConvParams& p; hipStream_t s;
+  static hipError_t none() { return hipErrorInvalidValue; }
+  template <int EK, int ID> hipError_t run() const {
+    constexpr KidRoute r = kid_route(ID, EK);
+    if constexpr (r.id != 0) return launch_one2<r.ek, r.id>(p, s); else return none();
+  }
+};
+hipError_t launch_conv_igemm2(int layer, int ek, const ConvParams& p, hipStream_t s) { return for_kernel_id(layer, ek, LaunchOp{p, s}); }
 
-template <int EK, int LAYER> static PackGeom geom2_of() {
-  using C = Cfg2<EK, LAYER>;
-  return PackGeom{C::CIN, C::COUT, C::COUT_PAD, C::CK, C::TG, C::NT, C::TH, C::KS, C::NPL, 0};
-}
-template <int EK> static PackGeom geom2_layer(int layer) {
-  switch (layer) {
-    case 1: return geom2_of<EK, 1>();
-    case 2: return geom2_of<EK, 2>();
-    case 3: return geom2_of<EK, 3>();
-    case 4: return geom2_of<EK, 4>();
-    case 5: return geom2_of<EK, 5>();
-    case 6: return geom2_of<EK, 6>();
-    case 7: return geom2_of<EK, 7>();
-    case 8: return geom2_of<EK, 8>();
-    case 9: return geom2_of<EK, 9>();
-    case 10: return geom2_of<EK, 10>();
-    case 11: return geom2_of<EK, 11>();
-    case 12: return geom2_of<EK, 12>();
-    case 13: return geom2_of<EK, 13>();
-    case 14: return geom2_of<EK, 14>();
-    case 15: return geom2_of<EK, 15>();
-    case 16: return geom2_of<EK, 16>();
-    case 17: return geom2_of<EK, 17>();
-    case 18: return geom2_of<EK, 18>();
-    case 20: return geom2_of<EK, 20>();
-    case 21: return geom2_of<EK, 21>();
-    case 22: return geom2_of<EK, 22>();
-    case 24: return geom2_of<EK, 24>();
-    case 25: return geom2_of<EK, 25>();
-    case 26: return geom2_of<EK, 26>();
-    case 30: return geom2_of<EK, 30>();
-    case 31: return geom2_of<EK, 31>();
-    case 32: return geom2_of<EK, 32>();
-    case 33: return geom2_of<EK, 33>();
-    case 34: return geom2_of<EK, 34>();
-    case 35: return geom2_of<EK, 35>();
-    case 36: return geom2_of<EK, 36>();
-    case 37: return geom2_of<EK, 37>();
-    case 38: return geom2_of<EK, 38>();
-    case 39: return geom2_of<EK, 39>();
-    case 40: return geom2_of<EK, 40>();
-    case 41: return geom2_of<EK, 41>();
-    case BIG_CONV3C: if constexpr (EK != EK_F32) return geom2_of<EK, BIG_CONV3C>(); else return geom2_of<EK, 8>();      // same packed image as layers 8 / 9, th = 16
-    case BIG_CONV3H: if constexpr (EK != EK_F32) return geom2_of<EK, BIG_CONV3H>(); else return geom2_of<EK, 9>();
-    case ONE_CONV3H: return geom2_of<EK, 9>();
-    case SWIN_CONVA_H: return geom2_of<EK, 5>();          // same packed images as layers 5 / 7
-    case SWIN_PRED_H: return geom2_of<EK, 7>();
-    case SWIN_PRED5_H: return geom2_of<EK, SWIN_PRED5_H>();
-    case SWIN_PRED5B_H: if constexpr (EK != EK_F32) return geom2_of<EK, SWIN_PRED5B_H>(); else return geom2_of<EK, SWIN_PRED5_H>();      // same packed image, th = 16
-    case 54: return geom2_of<EK, 54>();
-    case 55: return geom2_of<EK, 55>();
-    case 56: return geom2_of<EK, 56>();
-    case 57: return geom2_of<EK, 57>();
-    case 58: return geom2_of<EK, 58>();
-    case 59: return geom2_of<EK, 59>();
-    case 60: return geom2_of<EK, 60>();
-    case 61: return geom2_of<EK, 61>();
-    case 62: return geom2_of<EK, 62>();
-    case 63: return geom2_of<EK, 63>();
-    case 64: return geom2_of<EK, 64>();
-    case 65: return geom2_of<EK, 65>();
-    default: return geom2_of<EK, 23>();
-  }
-}
-static PackGeom geom2_layer_split(int layer) {
-  switch (layer) {
-#define DD_SPLIT_CASE(L) case L: return geom2_of<EK_F16S, L>();
-    DD_SPLIT_CASE(10) DD_SPLIT_CASE(11) DD_SPLIT_CASE(12) DD_SPLIT_CASE(13) DD_SPLIT_CASE(14) DD_SPLIT_CASE(15) DD_SPLIT_CASE(16) DD_SPLIT_CASE(17) DD_SPLIT_CASE(18)
-    DD_SPLIT_CASE(24) DD_SPLIT_CASE(25) DD_SPLIT_CASE(26)
-    DD_SPLIT_CASE(30) DD_SPLIT_CASE(31) DD_SPLIT_CASE(32) DD_SPLIT_CASE(33) DD_SPLIT_CASE(34) DD_SPLIT_CASE(35) DD_SPLIT_CASE(36) DD_SPLIT_CASE(37) DD_SPLIT_CASE(38) DD_SPLIT_CASE(39) DD_SPLIT_CASE(40) DD_SPLIT_CASE(41)
-    DD_SPLIT_CASE(54) DD_SPLIT_CASE(55) DD_SPLIT_CASE(56) DD_SPLIT_CASE(57) DD_SPLIT_CASE(58) DD_SPLIT_CASE(59) DD_SPLIT_CASE(60) DD_SPLIT_CASE(61) DD_SPLIT_CASE(62) DD_SPLIT_CASE(63) DD_SPLIT_CASE(64) DD_SPLIT_CASE(65)
-#undef DD_SPLIT_CASE
-    case 1: return geom2_of<EK_F16S, 1>();
-    case 2: return geom2_of<EK_F16S, 2>();
-    case 3: return geom2_of<EK_F16S, 3>();
-    case 4: return geom2_of<EK_F16S, 4>();
-    case 5: return geom2_of<EK_F16S, 5>();
-    case 6: return geom2_of<EK_F16S, 6>();
-    case 7: return geom2_of<EK_F16S, 7>();
-    case 8: case CONV3C_NCHW: return geom2_of<EK_F16S, 8>();
-    case SWIN_CONVA_H: return geom2_of<EK_F16S, 5>();
-    case SWIN_PRED5_H: return geom2_of<EK_F16S, SWIN_PRED5_H>();
-    default: return geom2_of<EK_F16S, 9>();
-  }
-}
-PackGeom conv_pack_geom2(int layer, int ek) {
-  switch (ek) {
-    case EK_F16R: {      // conv1: the split image; conv4: the f16 geometry with the lo halves stacked into the padding cout rows; else f16
-      if (layer == 1) return geom2_of<EK_F16S, 1>();
-      PackGeom g = geom2_layer<EK_F16>(layer);
-      if (layer == 4) g.stack = 1;
-      return g;
+struct GeomOp {
+  static PackGeom none() { return PackGeom{}; }
+  template <int EK, int ID> PackGeom run() const {
+    constexpr KidRoute r = kid_image(ID, EK);
+    if constexpr (r.id != 0) {
+      using C = Cfg2<r.ek, r.id>;
+      return PackGeom{C::CIN, C::COUT, C::COUT_PAD, C::CK, C::TG, C::NT, C::TH, C::KS, C::NPL, (EK == EK_F16R && ID == KID_CONV4) ? 1 : 0};      // (conv4, EK_F16R: the lo halves stacked into the padding cout rows)
+    } else {
+      return none();
     }
-    case EK_F16S: return geom2_layer_split(layer);
-    case EK_F32: return geom2_layer<EK_F32>(layer);
-    case EK_BF16: case EK_BF16M: return geom2_layer<EK_BF16>(layer);     // 2-byte kinds share one geometry
-    default: return geom2_layer<EK_F16>(layer);
   }
-}
+};
+PackGeom conv_pack_geom2(int layer, int ek) { return for_kernel_id(layer, ek, GeomOp{}); }
 
 }  // namespace dd

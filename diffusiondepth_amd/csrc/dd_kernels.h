@@ -126,40 +126,8 @@ struct ConvParams {
 };
 
 // ---- fused implicit-GEMM path (dd_igemm2.hip) ------------------------------------------------
-// layer ids: see dd_igemm2_cfg.h; ek: element kind.  Weights are packed with the LDS swizzle pre-applied
+// kernel ids (`layer`): dd_kernel_ids.h (included at the end of this header); ek: element kind.  Weights are packed with the LDS swizzle pre-applied
 // (16-B piece j of block row r is stored at j ^ ((r / (256/rowbytes)) & (rowbytes/16 - 1))).
-// Kernel ids of the BIG-TILE forms of the hoisted conv3 pair (dd_igemm2_cfg.h): layer 8 (conv3(cond), once per image) and layer 9 (conv3 in
-// the loop) on 16x32-pixel tiles -- four waves of 128 pixels x 64 couts each, 0.75 instead of 1.0 LDS fragment reads per MFMA, half the
-// weight stream per pixel -- chosen per launch when there are more 8x32 tiles than resident workgroup slots (the two must agree: layer 8
-// leaves its result in the accumulator-fragment order of layer 9's tiles).  Same packed weights as layers 8 / 9.
-constexpr int BIG_CONV3C = 48, BIG_CONV3H = 49;
-// layer 9 on its 8x32 tiles with ONE patch buffer (dd_igemm2_cfg.h, ONEBUF): the next chunk's patch goes into the buffer the MFMAs just read, behind a
-// second workgroup barrier per stage; 52 KB of LDS = three workgroups per CU.  Same tiles, packed weights and accumulator-fragment order as layer 9.
-constexpr int ONE_CONV3H = 46;
-// layer 8 (the once-per-image conv3(cond)) reading the caller's NCHW fp32 condition tensor DIRECTLY: a staging item's eight channels are eight
-// 4-byte loads from eight channel planes (consecutive lanes = consecutive pixels of one plane: whole 128-byte segments) instead of two 16-byte
-// loads from the channel-blocked copy -- the copy (438 MB read + 438 MB written per four KITTI maps: 189 us of a 7.5-ms step in the refined f16
-// mode) is not made at all.  Split-f16 kernel only (the refined mode's hoisted plans with an explicit condition tensor); same tiles, packed
-// weights, arithmetic and output order as layer 8 in that kind -- bit-identical results.
-constexpr int CONV3C_NCHW = 47;
-// Swin / MPViT denoiser, forward-only plans: upsample_fuse (convA, convB: no norm, no activation) and pred.0 are ONE linear map of
-// s = up(feat) + E[t] + NE(x_t) (reference ...swin_addHAHI.py:321-333,378-380), so
-//   pred.0(convB(convA(s))) = W3*WB*WA*NE(x_t)  +  [W3*(WB*(WA*up(feat) + a) + b)]  +  W3*WB*WA*(E[t] on every pixel)  + b3
-// with every convolution zero-padding its own input as the reference's does.  The bracket is computed ONCE per image (layer 6 kernel on
-// convA's and convB's weights, then layer 8: accumulator-fragment order, as the Res variant's hoisted conv3(cond)); the E[t] term is constant
-// over the image except within three pixels of its border: a table per loop step with one row per border class (swin_ttab, dd_misc.hip).
-//   SWIN_CONVA_H = convA on relu(gn2(y2)) alone (layer 5 without the condition / embedding addends, no bias)
-//   SWIN_PRED_H  = pred.0 (layer 7) whose accumulators start at the hoisted term and whose epilogue adds the table rows
-constexpr int SWIN_CONVA_H = 50, SWIN_PRED_H = 52;
-//   SWIN_PRED5_H = pred.0 and convB as ONE 5x5 convolution 256 -> 64 on convA's result (W5[u] = sum over e + d = u of W3[e] . WB[d], built per
-//   parameter generation by swin_compose, dd_misc.hip): 0.82 instead of 1.47 MFLOP per pixel and step and no convB result in HBM.  The 5x5
-//   form also sums, at the pixels ON the image border, the terms W3[e] . convB(.)(q + e) for taps e that leave the image -- which the
-//   reference's pred.0 zero-pads away; they are computed per step from the border rows / columns of convA's result (swin_bcorr: ring
-//   buffer ConvParams::bcorr) and subtracted in the epilogue.  Accumulator start values and E[t] rows as SWIN_PRED_H.
-constexpr int SWIN_PRED5_H = 53;
-// the same on 16x32-pixel tiles (the tiling of BIG_CONV3C / BIG_CONV3H: half the weight stream per pixel, 40 MFMAs per stage, 0.75 LDS reads per
-// MFMA), picked with the same rule (plan_big_tiles, dd_api.cpp); its accumulator start values come from BIG_CONV3C
-constexpr int SWIN_PRED5B_H = 51;
 // ring buffer of the border pixels of an h x w image: top row, bottom row, left column, right column (without the corners)
 __host__ __device__ inline int swin_ring_size(int h, int w) { return 2 * w + 2 * (h > 2 ? h - 2 : 0); }
 __host__ __device__ inline int swin_ring_stride(int h, int w) { return swin_ring_size(h, w) + 4; }      // + one entry per corner: its sideways taps (swin_bcorr_line_kernel)
@@ -181,6 +149,7 @@ inline int persist_grid(int B, int tiles_per_img, int slots) {
 struct PackGeom { int cin, cout, cout_pad, ck, tg, nt, th, ks, planes, stack; };   // th = output tile height (tile width is 32), ks = kernel size,
                                                                             // planes = 2: split f16 image, every stage block = [hi | lo];
                                                                             // stack = 1 (conv4, EK_F16R): cout rows cout..2 cout-1 = the lo halves times STACK_LSCALE
+// a (layer, ek) pair that no kernel runs (kid_route, dd_kernel_ids.h): launch_conv_igemm2 returns hipErrorInvalidValue, conv_pack_geom2 an all-zero PackGeom
 hipError_t launch_conv_igemm2(int layer, int ek, const ConvParams& p, hipStream_t s);
 // conv4 (64 -> 16) as a persistent streaming kernel (dd_thin.hip): same ConvParams and packed weights as layer 4; ek = EK_F16 / EK_BF16
 //   stack = the stacked hi / lo weight image (EK_F16R); in_q15 = y3 arrives as int16 with a per-pixel scale (ConvParams::cadd_scale = that scale
@@ -299,3 +268,5 @@ hipError_t launch_naive_axpby(const float* x, const float* eps, const float* c1c
                               long long n, hipStream_t s);
 
 }  // namespace dd
+
+#include "dd_kernel_ids.h"

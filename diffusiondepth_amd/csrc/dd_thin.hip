@@ -46,7 +46,7 @@ constexpr int TAB_BYTES = (2 * CIN + NROW) * 4 + WAVES * 8 * 8;
 constexpr int smem_bytes(bool psplit) { return W_BYTES + 2 * (psplit ? 2 : 1) * PATCH_PLANE + TAB_BYTES; }
 static_assert(smem_bytes(true) <= 80 * 1024, "two workgroups per CU");
 static_assert(NCH == 4 && NIT == 2 && (NCH % 2) == 0, "rolling prefetch below is written for four chunks");
-static_assert(Cfg2<EK_F16, 4>::CK == CK && Cfg2<EK_F16, 4>::TG == 9 && Cfg2<EK_F16, 4>::NT == NROW && Cfg2<EK_F16, 4>::W_BYTES == W_STAGE,
+static_assert(Cfg2<EK_F16, KID_CONV4>::CK == CK && Cfg2<EK_F16, KID_CONV4>::TG == 9 && Cfg2<EK_F16, KID_CONV4>::NT == NROW && Cfg2<EK_F16, KID_CONV4>::W_BYTES == W_STAGE,
               "the packed weight image of layer 4 (dd_igemm2_cfg.h, DD_C4_CK16) is read as it is");
 }  // namespace thin
 

@@ -266,7 +266,12 @@ int dd_last_loop_ms(dd_handle_t h, float* ms);
 int dd_get_counter(dd_handle_t h, const char* key, int64_t* value);
 /* With option "layer_timing" = 1 the loop runs eagerly with a hipEvent pair around every
  * convolution launch; this returns the accumulated milliseconds and launch count of conv `layer`
- * (1..4 = conv1..conv4 of the Res denoiser; 5,6,7 = convA, convB, pred.0 of the Swin variant; 9 = conv3 with the hoisted condition term; 10..13 = conv_lateral[0..3], 14 = conv_up of dd_condition; 15..18 / 24..26 = the laterals of the Swin-L / MPViT pyramids; 20..23 = data-gradient convs) since the option was set (used by bench.py for the per-kernel roofline figure). */
+ * (a kernel id, 1..65: diffusiondepth_amd/csrc/dd_kernel_ids.h is the one table of them) since the option was set (used by bench.py for the per-kernel
+ * roofline figure).  The ids a caller asks for -- each the value of the KID_* constant of that header named beside it, which is where to check this list:
+ * 1..4 = conv1..conv4 of the Res denoiser (KID_CONV1..4); 5, 6, 7 = convA, convB, pred.0 of the Swin variant (KID_SWIN_CONVA / _CONVB / _PRED);
+ * 9 = conv3 with the hoisted condition term (KID_CONV3H); 10..13 = conv_lateral[0..3] (KID_FPN_LAT_RES + level), 14 = conv_up of dd_condition
+ * (KID_FPN_UP); 15..18 / 24..26 = the laterals of the Swin-L / MPViT pyramids (KID_FPN_LAT_SWIN / _MPVIT + level); 30..41 / 54..65 = the HAHI
+ * neck of dd_neck_condition (KID_NECK_SWIN / _MPVIT + 4 * kind + level).  The tile / hoisted forms (46..53) book under the layer they stand in for. */
 int dd_get_layer_ms(dd_handle_t h, int layer, double* total_ms, int64_t* launches);
 
 /* Copies an internal intermediate of the last dd_denoise_once call to a caller DEVICE buffer as

@@ -7,10 +7,12 @@
 
 extern "C" {
 
-// cin, cout, cout_pad, ck, tg, nt, th, ks of (layer, element kind): the packed-weight geometry the host side packs with
-void emu_geom2(int layer, int ek, int* out8) {
+// cin, cout, cout_pad, ck, tg, nt, th, ks, planes, stack of (layer, element kind): the packed-weight geometry the host side packs with (all zero: no
+// kernel runs the pair)
+void emu_geom2(int layer, int ek, int* out10) {
   const dd::PackGeom g = dd::conv_pack_geom2(layer, ek);
-  out8[0] = g.cin; out8[1] = g.cout; out8[2] = g.cout_pad; out8[3] = g.ck; out8[4] = g.tg; out8[5] = g.nt; out8[6] = g.th; out8[7] = g.ks;
+  out10[0] = g.cin; out10[1] = g.cout; out10[2] = g.cout_pad; out10[3] = g.ck; out10[4] = g.tg; out10[5] = g.nt; out10[6] = g.th; out10[7] = g.ks;
+  out10[8] = g.planes; out10[9] = g.stack;
 }
 
 int emu_conv2(int layer, int ek, const void* in, const void* wpack, const float* bias, void* out, double* stats_out, const double* stats_in,
@@ -22,6 +24,7 @@ int emu_conv2(int layer, int ek, const void* in, const void* wpack, const float*
   p.gn_beta = gn_beta; p.cond = cond; p.emb = emb; p.tvec = tvec; p.t_base = t_base; p.t_bstride = t_bstride; p.y4 = y4; p.xout = xout;
   p.c1c2 = c1c2; p.step = step; p.B = B; p.h = h; p.w = w; p.cadd = cadd; p.etab = etab; p.addend = addend;
   const dd::PackGeom g = dd::conv_pack_geom2(layer, ek);
+  if (g.th == 0) return (int)hipErrorInvalidValue;      // (the launcher would answer the same)
   p.tiles_x = (w + 31) / 32;
   p.tiles_y = (h + g.th - 1) / g.th;
   return dd::launch_conv_igemm2(layer, ek, p, nullptr);

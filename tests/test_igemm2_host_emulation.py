@@ -106,9 +106,9 @@ SPEC = {
 
 
 def run_layer(emu, layer, ek, *, B=1, h=11, w=37, order=0, late=0, seed=0, step=1, addend=False):
-    g8 = (ctypes.c_int * 8)()
-    emu.emu_geom2(layer, ek, g8)
-    geom = tuple(g8)
+    g10 = (ctypes.c_int * 10)()
+    emu.emu_geom2(layer, ek, g10)
+    geom = tuple(g10)[:8]
     cin, cout, cout_pad, ck, tg, nt, th, ks = geom
     pro, stats, out_f32, relu = SPEC[layer]
     rng = np.random.default_rng(seed + 31 * layer)
@@ -253,6 +253,31 @@ def test_data_gradient_layers(emu, layer):
 
 def test_batch_two_images(emu):
     run_layer(emu, 3, EK_F16, B=2, h=9, w=33, order=1, late=1)
+
+
+def test_kernel_table_matches_parent(emu):
+    """The generated dispatch (the id list and kid_route / kid_image of dd_kernel_ids.h) against tests/golden/kernel_table.json, minted from the
+    hand-written switches of the commit before it (tests/golden/make_golden_kernel_table.py): for EVERY (id, kind), id 0..71, kind 0..5 --
+    the launcher has a kernel for exactly the pairs it had (an empty launch, B = 0, returns 0 for those and hipErrorInvalidValue otherwise), every
+    routed pair packs with the same geometry, field for field, and a pair without a kernel gets the all-zero geometry (the old switches answered
+    those with layer 23's or layer 9's)."""
+    import json
+    import os
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kernel_table.json")) as f:
+        gold = json.load(f)
+    table = gold["geometry"]
+    assert len(table) == 6 and all(len(row) == 72 for row in table)
+    assert sum(g is not None for row in table for g in row) == 326 and gold["routed_per_kind"] == [53, 56, 56, 56, 49, 56]
+    wrong = []
+    for ek, row in enumerate(table):
+        for kid, want in enumerate(row):
+            rc = emu.emu_conv2(kid, ek, *([None] * 11), 0, 0, None, None, None, 0, 0, 8, 32, None, None, None)
+            g10 = (ctypes.c_int * 10)()
+            emu.emu_geom2(kid, ek, g10)
+            got = list(g10)
+            if (rc == 0) != (want is not None) or got != (want if want is not None else [0] * 10):
+                wrong.append((kid, ek, rc, got, want))
+    assert not wrong, "%d (id, kind, launch status, geometry, parent's geometry): %s" % (len(wrong), wrong[:8])
 
 
 def test_emulation_catches_a_lax_counted_wait(emu, tmp_path):
