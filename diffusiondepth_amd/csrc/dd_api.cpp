@@ -201,6 +201,15 @@ int dd_get_counter(dd_handle_t h, const char* key, int64_t* value) {
   else if (k == "cond_split_ok") *value = (h->fpn_committed && h->fpn_split_ok ? 1 : 0) | (h->neck_committed && h->neck_split_ok ? 2 : 0);   // bit 0: FPN, bit 1: neck weights fit the split-f16 images
   else if (k == "resident_slots") *value = h->resident_slots;      // workgroup slots at two per CU (2 x multiProcessorCount): what the tile rules compare tile counts with
   else if (k == "trajectory_reuses") *value = h->n_traj_reuse;
+  else if (k == "thin_stream_launches") *value = h->thin_stream_launches;
+  else if (k.compare(0, 13, "kid_launches:") == 0) {      // "kid_launches:<id>": <id> = a kernel id of dd_kernel_ids.h's list, in decimal
+    int id = 0;
+    const size_t n = k.size() - 13;
+    bool ok = n >= 1 && n <= 3 && !(n > 1 && k[13] == '0');
+    for (size_t i = 13; ok && i < k.size(); ++i) { ok = k[i] >= '0' && k[i] <= '9'; id = id * 10 + (k[i] - '0'); }
+    if (!ok || !kid_listed(id)) return h->fail(DD_ERR_INVALID_ARG, "dd_get_counter: '" + k + "' does not name a kernel id (dd_kernel_ids.h)");
+    *value = h->kid_launches[id];
+  }
   else return h->fail(DD_ERR_INVALID_ARG, "dd_get_counter: unknown key '" + k + "'");
   return DD_OK;
 }

@@ -297,6 +297,10 @@ struct dd_handle_s {
   double layer_ms[N_LAYER_SLOTS] = {0};     // index = kernel id - 1; a special form books under the id the caller launched it as (launch_conv's slot)
   int64_t layer_cnt[N_LAYER_SLOTS] = {0};
   std::vector<std::tuple<int, hipEvent_t, hipEvent_t>> pending_ev;
+  // counters "kid_launches:<id>" / "thin_stream_launches": launches ENQUEUED per kernel id (index = id; launch_conv, captures included; a graph replay
+  // enqueues nothing) and of the streaming conv4 of dd_thin.hip -- how a test establishes which kernel forms an option or a tile-count rule selected
+  int64_t kid_launches[KID_LAST + 1] = {0};
+  int64_t thin_stream_launches = 0;
 
   int fail(int code, const std::string& m) { err = m; return code; }
 };

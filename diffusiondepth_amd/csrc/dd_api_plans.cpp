@@ -147,6 +147,7 @@ bool conv_tiles(ConvParams& p, int kid, int ek) {
 int launch_conv(dd_handle_t h, int kid, int ek, ConvParams p, hipStream_t s, int slot) {
   if (!conv_tiles(p, kid, ek)) return h->fail(DD_ERR_INVALID_ARG, "no fused convolution kernel for kernel id " + std::to_string(kid) + " in element kind " + std::to_string(ek));
   DD_HIP(timed(h, slot, s, [&] { return launch_conv_igemm2(kid, ek, p, s); }));
+  h->kid_launches[kid_route(kid, ek).id]++;      // the instantiation that runs (kid_route: ONE_CONV3H is KID_CONV3H's kernel in the kinds without a one-buffer form); conv_tiles: it exists
   return DD_OK;
 }
 
@@ -283,6 +284,7 @@ int enqueue_fused_step(dd_handle_t h, Plan* pl, int step, const float* x_in, flo
       q.persist_slots = h->thin_slots;
       if (rf) q.cadd_scale = static_cast<const float*>(pl->slot(pl->y3_scale, step));
       DD_HIP(timed(h, layer, s, [&] { return rf ? launch_conv4_stream(EK_F16, q, s, true, pl->wide, pl->p4) : launch_conv4_stream(tk, q, s); }));
+      h->thin_stream_launches++;
       return DD_OK;
     }
     int lek = ek;

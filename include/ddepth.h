@@ -262,7 +262,12 @@ int dd_set_option(dd_handle_t h, const char* key, int64_t value);
 int dd_last_loop_ms(dd_handle_t h, float* ms);
 /* Counters: "graph_launches", "eager_loops", "graph_capture_failures", "plans", "neck_launches", "trajectory_ticket" (ticket of the
  * last dd_denoise call that kept its states), "trajectory_reuses" (dd_denoise_backward calls that read kept states), "lane_calls" (dd_denoise calls that ran as concurrent lanes),
- * "resident_slots" (workgroup slots at two per CU), "cond_split_ok" (bit 0 / 1: the committed FPN / neck weights fit the split-f16 images). */
+ * "resident_slots" (workgroup slots at two per CU), "cond_split_ok" (bit 0 / 1: the committed FPN / neck weights fit the split-f16 images),
+ * "kid_launches:<id>" (launches of the fused-convolution kernel id <id> -- decimal, an id listed in csrc/dd_kernel_ids.h, anything else is an error --
+ * ENQUEUED by this handle since dd_create: eager launches and the launches recorded while a graph is captured; a graph replay enqueues nothing, so
+ * read it around a call made with option "graph" = 0 to see which kernel forms a setting or a tile-count rule selects.  The id is the kernel that
+ * runs: a special form counts under its own id (46..53) although its time is booked under the layer it stands in for, dd_get_layer_ms),
+ * "thin_stream_launches" (the same for the persistent streaming conv4, which has no kernel id: such a step moves it instead of "kid_launches:4"). */
 int dd_get_counter(dd_handle_t h, const char* key, int64_t* value);
 /* With option "layer_timing" = 1 the loop runs eagerly with a hipEvent pair around every
  * convolution launch; this returns the accumulated milliseconds and launch count of conv `layer`

@@ -335,6 +335,28 @@ def test_big_tile_and_lane_paths_agree_with_the_single_image_path_at_kitti_size(
     # the automatic rule (round 6): the Res denoiser keeps its 8x32 tiles -- one-patch-buffer form when a plan's tiles exceed the resident slots -- whatever
     # the lane count (the 16x32 form under lanes lost 4-6 % on every box: profiles/r06_experiments.md section 2); per image the two 8x32 forms are bit-identical
     assert np.array_equal(auto, small)
+    # which kernels those were (counters "kid_launches:<id>": launches ENQUEUED, so one extra eager call of the same key each): the forced 16x32 pair
+    # 48 / 49 and none of the 8x32 forms; under the automatic rule the one-buffer form 46 (its lane of two images, or the whole batch, exceeds the
+    # resident slots) and no 16x32 tile
+    ids = (8, 9, 46, 48, 49)
+    read = lambda: {k: be.counter(f"kid_launches:{k}") for k in ids}
+    try:
+        be.set_option("graph", 0)
+        be.set_option("big_tiles", 1)
+        n0 = read()
+        big_eager = be.denoise(x, cond, T, "bf16")
+        n1 = read()
+        be.set_option("big_tiles", -1)
+        auto_eager = be.denoise(x, cond, T, "bf16")
+        n2 = read()
+    finally:
+        be.set_option("big_tiles", -1)
+        be.set_option("graph", 1 if be.graph_replay else 0)
+    forced, rule = {k: n1[k] - n0[k] for k in ids}, {k: n2[k] - n1[k] for k in ids}
+    U.record("batch_vs_solo_kitti_kernel_ids", forced_big_tiles={str(k): v for k, v in forced.items()}, automatic={str(k): v for k, v in rule.items()})
+    assert forced[48] > 0 and forced[49] > 0 and forced[8] == forced[9] == forced[46] == 0, forced
+    assert rule[46] > 0 and rule[48] == rule[49] == 0, rule
+    assert torch.isfinite(big_eager).all() and torch.isfinite(auto_eager).all()
 
 
 def test_refined_f16_reads_an_explicit_condition_tensor_in_place(U):

@@ -57,12 +57,26 @@ def maxabs(a, b):
     return float(np.abs(np.asarray(a, np.float64) - np.asarray(b, np.float64)).max())
 
 
+def conv3_launches(be):
+    """Launches enqueued so far of the hoisted conv3 pair's forms (counters "kid_launches:<id>"): 8 / 9, one-buffer 46, 16x32 tiles 48 / 49."""
+    return {k: be.counter(f"kid_launches:{k}") for k in (8, 9, 46, 48, 49)}
+
+
+def moved(before, after):
+    return {k for k in after if after[k] != before[k]}
+
+
 # ---- the denoiser against the reference's golden vectors ----------------------------------------------------------------------------------------
 def test_library_reports_itself_and_fails_loudly(lib, cases):
     be, _ = backend_for(lib, cases["denoise_res"])
     assert b"gfx950" in lib.dd_version()
     with pytest.raises(RuntimeError):
         be.set_option("no_such_option", 1)
+    # counters "kid_launches:<id>": every listed kernel id answers, anything else is an error like any other bad key
+    assert be.counter("kid_launches:48") >= 0 and be.counter("kid_launches:4") >= 0 and be.counter("thin_stream_launches") >= 0
+    for bad in ("kid_launches:", "kid_launches:0", "kid_launches:19", "kid_launches:66", "kid_launches:049", "kid_launches:4x", "kid_launches:-1", "kid_launches:4800"):
+        with pytest.raises(RuntimeError, match="kernel id"):
+            be.counter(bad)
     fresh = EmuDenoiser(lib, "res")
     with pytest.raises(RuntimeError, match="not committed"):
         fresh.denoise(np.zeros((1, 16, 8, 8)), np.zeros((1, 256, 8, 8)), 2)
@@ -328,13 +342,17 @@ def test_hoisted_conv3_with_one_patch_buffer(lib, prec):
     be.set_option("hoist_cond", 1)
     be.set_option("big_tiles", 0)
     be.set_option("one_buffer", 0)
+    n0 = conv3_launches(be)
     two = be.denoise(inp["x_T"], inp["cond"], T, prec)
+    n1 = conv3_launches(be)
     be.set_option("one_buffer", 2)
     outs = []
     for order, late in (((0, 0), (1, 0), (0, 1), (1, 1)) if FULL else ((0, 0), (1, 1))):
         be.timing(order=order, dma_late=late)
         outs.append(be.denoise(inp["x_T"], inp["cond"], T, prec))
+    n2 = conv3_launches(be)
     be.set_option("one_buffer", 1); be.set_option("big_tiles", -1)
+    assert moved(n0, n1) - {8} == {9} and moved(n1, n2) - {8} == {46}, (n0, n1, n2)      # (8: the once-per-image term of the f16 / bf16 modes; f16r reads the NCHW tensor, id 47)
     assert all(np.array_equal(outs[0], o) for o in outs[1:])
     assert np.array_equal(outs[0], two)
     assert maxabs(outs[0], ref) < LATENT_TOL[prec] * np.abs(ref).max()
@@ -351,11 +369,14 @@ def test_hoisted_conv3_on_16x32_tiles(lib, prec):
     be.set_option("big_tiles", 0)
     small = be.denoise(inp["x_T"], inp["cond"], T, prec)
     be.set_option("big_tiles", 1)
+    n0 = conv3_launches(be)
     outs = []
     for order, late in (((0, 0), (1, 0), (0, 1), (1, 1)) if FULL else ((0, 0), (1, 1))):
         be.timing(order=order, dma_late=late)
         outs.append(be.denoise(inp["x_T"], inp["cond"], T, prec))
+    n1 = conv3_launches(be)
     be.set_option("big_tiles", -1)
+    assert moved(n0, n1) == ({49} if prec == "f16r" else {48, 49}), (n0, n1)      # (f16r: split-f16 layer 8 from the NCHW tensor, reformatted into the 16x32 order)
     assert all(np.array_equal(outs[0], o) for o in outs[1:])
     assert maxabs(outs[0], ref) < LATENT_TOL[prec] * np.abs(ref).max()
     assert maxabs(outs[0], small) < LATENT_TOL[prec] * np.abs(ref).max()
