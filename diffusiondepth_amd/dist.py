@@ -366,10 +366,14 @@ class SyncBatchNorm(torch.nn.modules.batchnorm._BatchNorm):
         if input.dim() < 2:
             raise ValueError(f"expected at least 2D input (got {input.dim()}D input)")
 
+    def _exchanges(self) -> bool:
+        """The rule for when statistics are exchanged: .train(), an initialised group, and more than one rank (or force_sync)."""
+        return bool(self.training and dist.is_available() and dist.is_initialized()
+                    and (dist.get_world_size(self.process_group) > 1 or self.force_sync))
+
     def forward(self, x):
         self._check_input_dim(x)
-        sync = self.training and dist.is_available() and dist.is_initialized() and (dist.get_world_size(self.process_group) > 1 or self.force_sync)
-        if not sync:
+        if not self._exchanges():
             return super().forward(x)
         momentum = 0.0 if self.momentum is None else self.momentum
         if self.track_running_stats and self.num_batches_tracked is not None:

@@ -17,6 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import modules as _modules
+from .batchnorm import convert_hip_batchnorm, resolve_bn_backend
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
 from .necks import HAHIHeteroNeck
 from .scheduler import DDIMScheduler
@@ -49,7 +50,7 @@ class DDIMDepthEstimate_Res(nn.Module):
 
     def __init__(self, in_channels=(64, 128, 256, 512), up_scale_factor=1, inference_steps=20, num_train_timesteps=1000,
                  return_indices=None, depth_transform_cfg=None, depth_feature_dim=16, detach_fp=False, loss_cfgs=(),
-                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, **kwargs):
+                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, **kwargs):
         """Beyond the reference's keywords (src/model/diffusion_dcbase_model.py:77-91):
         profile            the two shipped configurations of a head (PROFILES below; None = $DDEPTH_PROFILE, else "reference"):
                              "reference" [default]  what the reference does, bit for bit where that is defined: fp32 arithmetic (the reference runs
@@ -68,7 +69,10 @@ class DDIMDepthEstimate_Res(nn.Module):
         loss_noise_device  "cpu" = draw the loss noise on the host and copy it over, as the reference does (…res.py:203, quirk q3: same
                            RNG stream as the reference); "device" = draw it on the GPU from a private generator of this head (same
                            distribution; saves the 6.8 MB-per-KITTI-map host RNG + H2D copy per forward: 15.6 -> 8.0 ms per KITTI eval
-                           forward); "auto" = "cpu" in .train() -- the reference's training RNG stream -- and "device" in eval."""
+                           forward); "auto" = "cpu" in .train() -- the reference's training RNG stream -- and "device" in eval.
+        bn_backend         "torch" [default] or "hip" (None = $DDEPTH_BN_BACKEND, else "torch"): with "hip" every BatchNorm2d of the FPN, the
+                           codec and the neck becomes a batchnorm.HipBatchNorm2d holding the same tensors, its ReLU / LeakyReLU fused, so
+                           the .train() forward and backward of those layers run in csrc/dd_bn.hip (same state-dict keys; eval unchanged)"""
         super().__init__()
         profile = profile or os.environ.get("DDEPTH_PROFILE") or "reference"      # (an empty DDEPTH_PROFILE means "not set")
         if profile not in PROFILES:
@@ -132,6 +136,12 @@ class DDIMDepthEstimate_Res(nn.Module):
                           and not (self.hahineck.cross_att or self.hahineck.self_att))        # (dd_neck_condition is the attention-off neck: what every head builds)
         if self._hip_neck:
             bound.register("hahineck.", self.hahineck)
+        self.bn_backend = resolve_bn_backend(bn_backend)
+        if self.bn_backend == "hip":
+            # (convup_fp never runs; it is converted too so that every BatchNorm of the head is handled alike)
+            for name in ("conv_lateral", "conv_up", "depth_transform", "hahineck", "convup_fp"):
+                if hasattr(self, name):
+                    setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
 
     @staticmethod
     def _on_hip(tensors) -> bool:
