@@ -26,6 +26,7 @@ from .model import Diffusion_DCbase_Model
 from .metric import Diffusion_DCbase_Metric, MetricAccumulator
 from .loss import Diffusion_DCbase_Loss
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
+from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv
 
 __all__ = [
     "DDIMScheduler", "HipDenoiser", "precision_id", "library_path", "load_library",
@@ -33,6 +34,6 @@ __all__ = [
     "DDIMDepthEstimate_Res", "DDIMDepthEstimate_Swin_ADD", "DDIMDepthEstimate_Swin_ADDHAHI", "DDIMDepthEstimate_MPVIT_ADDHAHI",
     "DDIMDepthEstimate_ResVis", "DDIMDepthEstimate_Swin_ADDHAHIVis", "HAHIHeteroNeck", "NLSPN", "Diffusion_DCbase_Model",
     "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
-    "HipBatchNorm2d", "convert_hip_batchnorm",
+    "HipBatchNorm2d", "convert_hip_batchnorm", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
 ]
 __version__ = "0.1.0"

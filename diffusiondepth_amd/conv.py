@@ -1,0 +1,300 @@
+"""The condition FPN's training convolutions, forward and backward, over the C ABI of include/ddepth_conv.h.
+
+What it is for: in .train() the condition FPN's ``conv_lateral[i]`` (Conv3x3 C_i -> 256, no bias) and ``conv_up[j]`` (ConvTranspose2d 256 -> 256,
+k2 s2, no bias) and their autograd run as fp32 MIOpen kernels, whatever the precision of the rest of the step.  ``HipConv2d`` and
+``HipConvTranspose2d`` run them through csrc/dd_conv.hip on the head's 16-bit MFMA operands (bf16, f16, or the split-f16 pair of "f16x3") with
+fp32 accumulation; only ``x`` and the weight are kept for the backward, and a gradient nobody needs is not computed.
+
+    convert_hip_conv(head.conv_lateral, "bf16")      # or: DDIMDepthEstimate_Res(..., conv_backend="hip") / DDEPTH_CONV_BACKEND=hip
+
+The library route is decided BEFORE the call and taken only when the input and the weight are contiguous fp32 tensors on a HIP device, the
+module's precision is "bf16", "f16" or "f16x3", and the channel counts are supported (multiples of 64 in 64..1536).  Everything else -- CPU
+tensors, the "fp32" / "f16r" / "naive_fp32" precisions, other dtypes or layouts -- calls the torch forward the module inherits.  It is never a
+fallback after an error, nothing is copied or converted silently, and there is no CPU library path.
+"""
+from __future__ import annotations
+
+import ctypes
+import os
+from typing import Dict, Optional, Tuple
+
+import torch
+import torch.nn as nn
+from torch.autograd import Function
+from torch.autograd.function import once_differentiable
+
+from . import backend
+
+# every symbol include/ddepth_conv.h declares (checked by tests/test_conv_cpu.py)
+ABI_SYMBOLS = ["dd_conv_last_error", "dd_conv_supported", "dd_conv_workspace_bytes", "dd_conv3x3_forward", "dd_conv3x3_backward_data",
+               "dd_conv3x3_backward_weight", "dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight"]
+
+OP_CONV3X3, OP_DECONV2X2 = 0, 1      # dd_conv_op
+LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
+_LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
+_ENTRY = {OP_CONV3X3: ("dd_conv3x3_forward", "dd_conv3x3_backward_data", "dd_conv3x3_backward_weight"),
+          OP_DECONV2X2: ("dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight")}
+
+_bound = None
+_workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _lib():
+    global _bound
+    if _bound is None:
+        lib = backend.load_library()
+        c_int, c_vp = ctypes.c_int, ctypes.c_void_p
+        lib.dd_conv_last_error.restype, lib.dd_conv_last_error.argtypes = ctypes.c_char_p, []
+        lib.dd_conv_supported.restype, lib.dd_conv_supported.argtypes = c_int, [c_int] * 4
+        lib.dd_conv_workspace_bytes.restype = c_int
+        lib.dd_conv_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+        for names in _ENTRY.values():
+            for n in names:
+                f = getattr(lib, n)
+                f.restype, f.argtypes = c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]
+        _bound = lib
+    return _bound
+
+
+def _ck(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed ({rc}): {_lib().dd_conv_last_error().decode()}")
+
+
+def _stream(t):
+    return int(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def precision_id(precision) -> Optional[int]:
+    """dd_precision of a precision name the library route runs, else None."""
+    pid = backend.PRECISIONS.get(str(precision).lower())      # (the aliases of backend.PRECISIONS count: "fp16", "split_f16")
+    return pid if pid in _LIBRARY_PRECISION_IDS else None
+
+
+def supported(op: int, cin: int, cout: int, precision) -> bool:
+    """dd_conv_supported: no device needed, no side effects."""
+    p = precision_id(precision)
+    return p is not None and bool(_lib().dd_conv_supported(int(op), int(cin), int(cout), p))
+
+
+def workspace_for(t: torch.Tensor, op: int, B: int, cin: int, cout: int, H: int, W: int, prec: int) -> torch.Tensor:
+    """The device scratch of one call (packed 16-bit weights, or the weight gradient's partial sums), cached per (device, bytes): a shape that
+    returns finds its buffer again, and the steady state allocates nothing.  Calls on one stream are ordered, so sites of equal size share a
+    buffer.  A first call inside a graph capture would allocate from the capture's pool: call once eagerly before capturing."""
+    need = ctypes.c_int64(0)
+    _ck(_lib().dd_conv_workspace_bytes(op, B, cin, cout, H, W, prec, ctypes.byref(need)), "dd_conv_workspace_bytes")
+    key = (t.device.index if t.device.index is not None else torch.cuda.current_device(), int(need.value))
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = torch.empty(int(need.value), dtype=torch.uint8, device=t.device)
+        _workspaces[key] = ws
+    return ws
+
+
+def _check_native(t: torch.Tensor, name: str):
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} is on {t.device}: the HIP convolution runs only on a HIP device (there is no CPU library path)")
+    if t.dtype != torch.float32 or not t.is_contiguous():
+        raise RuntimeError(f"{name} must be a contiguous fp32 tensor (got {t.dtype}, contiguous={t.is_contiguous()})")
+
+
+def _geometry(op: int, x: torch.Tensor, w: torch.Tensor):
+    """(B, Cin, Cout, H, W) of the forward, H, W = input size; checks that x and w belong together."""
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(f"expected 4D input and weight (got {x.dim()}D, {w.dim()}D)")
+    B, cin, H, W = (int(s) for s in x.shape)
+    if op == OP_CONV3X3:
+        cout, wcin, k = int(w.shape[0]), int(w.shape[1]), 3
+    else:
+        wcin, cout, k = int(w.shape[0]), int(w.shape[1]), 2
+    if wcin != cin or tuple(w.shape[2:]) != (k, k):
+        raise ValueError(f"weight {tuple(w.shape)} does not fit input {tuple(x.shape)}")
+    return B, cin, cout, H, W
+
+
+def _call(op, which, a, b, out, dims, prec):
+    B, cin, cout, H, W = dims
+    with torch.cuda.device(a.device):
+        ws = workspace_for(a, op, B, cin, cout, H, W, prec)
+        name = _ENTRY[op][which]
+        _ck(getattr(_lib(), name)(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, prec, _stream(a)), name)
+    return out
+
+
+# ---- the three directions, one function each (what the tests and tools drive; the autograd Function below is built from them) -----------------
+def conv_forward(op: int, x: torch.Tensor, w: torch.Tensor, prec: int) -> torch.Tensor:
+    _check_native(x, "x")
+    _check_native(w, "weight")
+    dims = _geometry(op, x, w)
+    B, _, cout, H, W = dims
+    s = 1 if op == OP_CONV3X3 else 2
+    return _call(op, 0, x, w, torch.empty((B, cout, s * H, s * W), dtype=torch.float32, device=x.device), dims, prec)
+
+
+def conv_backward_data(op: int, grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int) -> torch.Tensor:
+    _check_native(grad_y, "grad_y")
+    _check_native(w, "weight")
+    grad_x = torch.empty(tuple(x_shape), dtype=torch.float32, device=grad_y.device)
+    return _call(op, 1, grad_y, w, grad_x, _geometry(op, grad_x, w), prec)
+
+
+def conv_backward_weight(op: int, x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int) -> torch.Tensor:
+    _check_native(x, "x")
+    _check_native(grad_y, "grad_y")
+    grad_w = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
+    return _call(op, 2, x, grad_y, grad_w, _geometry(op, x, grad_w), prec)
+
+
+def _forward(ctx, op, x, weight, prec):
+    ctx.save_for_backward(x, weight)
+    ctx.conf = (int(op), int(prec))
+    return conv_forward(op, x, weight.detach(), int(prec))
+
+
+def _backward(ctx, grad_y):
+    x, weight = ctx.saved_tensors
+    op, prec = ctx.conf
+    need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+    if not (need_x or need_w):
+        return None, None, None
+    gy = grad_y.detach()
+    if gy.dtype != torch.float32 or not gy.is_contiguous():
+        gy = gy.float().contiguous()
+    gx = conv_backward_data(op, gy, weight.detach(), x.shape, prec) if need_x else None      # not for a detached input
+    gw = conv_backward_weight(op, x, gy, weight.shape, prec) if need_w else None             # not for a frozen weight
+    return gx, gw, None
+
+
+class Conv3x3Function(Function):
+    """(x, weight, dd_precision) -> F.conv2d(x, weight, None, 1, 1) over the three dd_conv3x3_* calls.  Kept for the backward: x and weight.  A
+    gradient ``ctx.needs_input_grad`` does not ask for is not computed.  Nothing synchronises the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight, prec):
+        return _forward(ctx, OP_CONV3X3, x, weight, prec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        return _backward(ctx, grad_y)
+
+
+class ConvTranspose2x2Function(Function):
+    """(x, weight, dd_precision) -> F.conv_transpose2d(x, weight, None, 2) over the three dd_deconv2x2_* calls; as Conv3x3Function."""
+
+    @staticmethod
+    def forward(ctx, x, weight, prec):
+        return _forward(ctx, OP_DECONV2X2, x, weight, prec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        return _backward(ctx, grad_y)
+
+
+def _tensors_native(x: torch.Tensor, w: torch.Tensor) -> bool:
+    return bool(x.is_cuda and w.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous()
+                and w.is_contiguous() and x.numel() > 0)
+
+
+def _pair(v):
+    return tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+
+
+def _plain(m) -> bool:
+    """No bias, groups 1, dilation 1, zero padding mode: what both operators of the library assume."""
+    return m.bias is None and m.groups == 1 and _pair(m.dilation) == (1, 1) and getattr(m, "padding_mode", "zeros") == "zeros"
+
+
+def _is_conv3x3(m) -> bool:
+    return (isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and _plain(m) and _pair(m.kernel_size) == (3, 3)
+            and _pair(m.stride) == (1, 1) and m.padding != "same" and _pair(m.padding) == (1, 1))
+
+
+def _is_deconv2x2(m) -> bool:
+    return (isinstance(m, nn.ConvTranspose2d) and _plain(m) and _pair(m.kernel_size) == (2, 2) and _pair(m.stride) == (2, 2)
+            and _pair(m.padding) == (0, 0) and _pair(m.output_padding) == (0, 0))
+
+
+class HipConv2d(nn.Conv2d):
+    """``nn.Conv2d(cin, cout, 3, 1, 1, bias=False)`` (same parameter, same state-dict key) whose forward and backward on a HIP device run in
+    csrc/dd_conv.hip on ``precision`` operands ("bf16", "f16", "f16x3"); every other precision and every tensor the library does not take
+    (module docstring) runs the inherited torch forward."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False, precision="fp32", **kwargs):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias=bias, **kwargs)
+        self.precision = precision
+
+    def extra_repr(self):
+        return super().extra_repr() + f", precision={self.precision}"
+
+    def _native(self, x) -> bool:
+        return bool(_is_conv3x3(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels
+                    and supported(OP_CONV3X3, self.in_channels, self.out_channels, self.precision))
+
+    def forward(self, x):
+        if not self._native(x):
+            return super().forward(x)
+        return Conv3x3Function.apply(x, self.weight, precision_id(self.precision))
+
+
+class HipConvTranspose2d(nn.ConvTranspose2d):
+    """``nn.ConvTranspose2d(cin, cout, 2, 2, bias=False)``; as HipConv2d."""
+
+    def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, padding=0, output_padding=0, bias=False, precision="fp32", **kwargs):
+        super().__init__(in_channels, out_channels, kernel_size, stride, padding, output_padding, bias=bias, **kwargs)
+        self.precision = precision
+
+    def extra_repr(self):
+        return super().extra_repr() + f", precision={self.precision}"
+
+    def _native(self, x, output_size) -> bool:
+        return bool(output_size is None and _is_deconv2x2(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels
+                    and supported(OP_DECONV2X2, self.in_channels, self.out_channels, self.precision))
+
+    def forward(self, x, output_size=None):
+        if not self._native(x, output_size):
+            return super().forward(x, output_size)
+        return ConvTranspose2x2Function.apply(x, self.weight, precision_id(self.precision))
+
+
+def eligible(m: nn.Module, precision) -> bool:
+    """3x3 s1 p1 or transpose k2 s2, no bias, groups 1, dilation 1, and channel counts and a precision dd_conv_supported accepts."""
+    if isinstance(m, (HipConv2d, HipConvTranspose2d)):
+        return False
+    if _is_conv3x3(m):
+        return supported(OP_CONV3X3, m.in_channels, m.out_channels, precision)
+    if _is_deconv2x2(m):
+        return supported(OP_DECONV2X2, m.in_channels, m.out_channels, precision)
+    return False
+
+
+def _from_conv(m, precision):
+    cls = HipConvTranspose2d if isinstance(m, nn.ConvTranspose2d) else HipConv2d
+    out = cls.__new__(cls)
+    nn.Module.__init__(out)
+    out.__dict__.update({k: v for k, v in m.__dict__.items() if k not in ("_parameters", "_buffers", "_modules")})
+    out._parameters.update(m._parameters)      # the SAME tensors: optimizers built before the conversion stay valid
+    out._buffers.update(m._buffers)
+    out.precision = precision
+    return out
+
+
+def convert_hip_conv(module: nn.Module, precision) -> nn.Module:
+    """Every eligible convolution of ``module`` (see ``eligible``) becomes a ``HipConv2d`` / ``HipConvTranspose2d`` holding the SAME parameter
+    tensor under the same name: state-dict keys and the indices inside an ``nn.Sequential`` do not change.  With a precision the library does
+    not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced."""
+    out = _from_conv(module, precision) if eligible(module, precision) else module
+    for name, child in list(module.named_children()):
+        new = convert_hip_conv(child, precision)
+        if new is not child:
+            setattr(out, name, new)
+    return out
+
+
+def resolve_conv_backend(conv_backend: Optional[str] = None) -> str:
+    """The head keyword ``conv_backend`` / the environment variable DDEPTH_CONV_BACKEND: "torch" (default; empty or absent) or "hip"."""
+    choice = conv_backend or os.environ.get("DDEPTH_CONV_BACKEND") or "torch"
+    if choice not in ("torch", "hip"):
+        raise ValueError(f"conv_backend must be 'torch' or 'hip' (got {choice!r})")
+    return choice

@@ -1,0 +1,410 @@
+// dd_conv.hip -- the training convolutions of the condition FPN as implicit-GEMM HIP kernels for gfx950 (include/ddepth_conv.h): Conv3x3 s1 p1
+// and ConvTranspose2d k2 s2, both without bias; forward, data gradient and weight gradient.  Tensors are contiguous fp32 NCHW as torch holds
+// them; the operands are rounded to 16 bits on the way into LDS and contracted on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulation.
+//
+// Structure:
+//   dd_conv_pack_kernel     the raw fp32 weights -> wp[tap][n][k] in 16 bits (hi, and lo in the split-f16 mode) in the workspace, on EVERY call
+//                           (the parameters change every optimiser step).  The data gradients are the same GEMM on the transposed (3x3: and
+//                           flipped) weights, so this kernel is all that tells the directions apart.
+//   dd_conv_igemm_kernel    D[n][pixel] += wp[tap][n][k] . patch[pixel + tap][k].  A workgroup owns a 4 x 32 pixel tile and 64 output channels,
+//                           wave w the tile's row w: the weights are the MFMA's A operand (read from global / L2, 16 bytes per lane), 32
+//                           consecutive pixels of a row its B operand, so lane l of the accumulator holds pixel l % 32 and every store
+//                           instruction writes 32 consecutive floats of one output plane.  The input patch with its halo is converted into
+//                           LDS KC channels at a time, consecutive lanes reading consecutive pixels of one NCHW plane; outside the image it is
+//                           zero.  <KS, S, PAD>: 3x3 forward / data gradient <3, 1, 1>; transpose-convolution forward <1, 1, 0> with N = 4 Cout
+//                           and an epilogue that writes pixel (2y + dy, 2x + dx); its data gradient <2, 2, 0>, which gathers those four.
+//   dd_conv_wgrad_kernel    D[p][q][tap] += P[p][pixel] . Q[q][pixel * S + tap]: a GEMM over the pixel dimension (the MFMA's K = 16 consecutive
+//                           pixels of a row).  A workgroup owns 64 x 64 channels and every tap, and a contiguous range of pixel tiles (a SPLIT);
+//                           it stores its partial into the workspace, and dd_conv_wgrad_reduce_kernel adds the splits in a fixed order.  No
+//                           floating-point atomics: two calls give the same bits.
+//
+// Plain HIP C++ and compiler builtins; every write to memory is a plain C++ store.  Only constructs the host emulation of the tests provides.
+#include "dd_conv.h"
+
+namespace ddconv {
+
+namespace {
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
+typedef __attribute__((ext_vector_type(8))) uint16_t u16x8_t;
+typedef __attribute__((ext_vector_type(16))) float f32x16_t;
+
+constexpr int kFillBatch = 8;      // global loads a thread has in flight while it fills LDS (one wave per SIMD cannot hide them otherwise)
+
+__device__ __forceinline__ uint16_t f32_to_bf16(float f) {      // round to nearest even
+  uint32_t u = __builtin_bit_cast(uint32_t, f);
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return (uint16_t)(u >> 16);
+}
+
+// one fp32 value -> its 16-bit operand(s): the rounded value, or the f16 pair hi = f16(v), lo = f16(v - hi) of the split mode
+template <int PREC>
+__device__ __forceinline__ void to_operand(float v, uint16_t& hi, uint16_t& lo) {
+  if constexpr (PREC == kPrecBf16) {
+    hi = f32_to_bf16(v);
+    lo = 0;
+  } else {
+    const _Float16 h = (_Float16)v;
+    hi = __builtin_bit_cast(uint16_t, h);
+    if constexpr (PREC == kPrecF16x3) lo = __builtin_bit_cast(uint16_t, (_Float16)(v - (float)h));
+    else lo = 0;
+  }
+}
+
+template <int PREC>
+__device__ __forceinline__ f32x16_t mma(const uint4& a, const uint4& b, f32x16_t acc) {
+  if constexpr (PREC == kPrecBf16) return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), acc, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), acc, 0, 0, 0);
+}
+
+// acc += a . b with a = ah + al, b = bh + bl: one MFMA, or hi.hi + hi.lo + lo.hi in the split mode
+template <int PREC>
+__device__ __forceinline__ f32x16_t mma_pair(const uint4& ah, const uint4& al, const uint4& bh, const uint4& bl, f32x16_t acc) {
+  acc = mma<PREC>(ah, bh, acc);
+  if constexpr (PREC == kPrecF16x3) {
+    acc = mma<PREC>(ah, bl, acc);
+    acc = mma<PREC>(al, bh, acc);
+  }
+  return acc;
+}
+
+// ---- weights -> wp[tap][n][k], 16 bits ----------------------------------------------------------------------------------------------------------
+enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3 };
+
+template <int PREC>
+__global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __restrict__ w, uint16_t* __restrict__ wh, uint16_t* __restrict__ wl,
+                                                                int mode, int N, int K, int taps) {
+  const size_t total = (size_t)taps * N * K;
+  const size_t idx = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= total) return;
+  const int k = (int)(idx % K), n = (int)((idx / K) % N), t = (int)(idx / ((size_t)K * N));
+  size_t src;
+  if (mode == kPackConvFwd) {             // w[co = n][ci = k][tap]
+    src = ((size_t)n * K + k) * 9 + t;
+  } else if (mode == kPackConvBwd) {      // w'[ci = n][co = k][ky][kx] = w[co][ci][2 - ky][2 - kx]
+    src = ((size_t)k * N + n) * 9 + (8 - t);
+  } else if (mode == kPackDeconvFwd) {    // n = (dy * 2 + dx) * Cout + co;  w[ci = k][co][dy][dx]
+    const int cout = N / 4, t4 = n / cout, co = n - t4 * cout;
+    src = ((size_t)k * cout + co) * 4 + t4;
+  } else {                                // w[ci = n][co = k][tap]
+    src = ((size_t)n * K + k) * 4 + t;
+  }
+  uint16_t hi, lo;
+  to_operand<PREC>(w[src], hi, lo);
+  wh[idx] = hi;
+  if constexpr (PREC == kPrecF16x3) wl[idx] = lo;
+}
+
+// ---- forward and data gradient --------------------------------------------------------------------------------------------------------------------
+// in [B][K][Hin][Win], wp [KS * KS][N][K]; grid (tiles, N / 64, B).  The tile grid is Ht x Wt pixels:
+//   !SCATTER: out [B][N][Ht][Wt], pixel (y, x) of the tile grid reads input pixels (y * S - PAD + ky, x * S - PAD + kx)
+//   SCATTER:  out [B][N / 4][2 Ht][2 Wt], GEMM column n = (dy * 2 + dx) * (N / 4) + co goes to pixel (2y + dy, 2x + dx) of plane co
+template <int PREC, int KS, int S, int PAD, int KC, bool SCATTER>
+__global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __restrict__ in, const uint16_t* __restrict__ wh,
+                                                                 const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N,
+                                                                 int Hin, int Win, int Ht, int Wt, int tiles_x) {
+  constexpr int PH = (kTileH - 1) * S + KS, PW = (kTileW - 1) * S + KS, PP = PH * PW;
+  constexpr int PS = KC + 8;      // halfs per patch pixel: a multiple of 8, so every 16-byte read is aligned
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  __shared__ uint16_t patch[NL][PP * PS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x, n0 = blockIdx.y * kTileN, b = blockIdx.z;
+  const int iy0 = ty * kTileH * S - PAD, ix0 = tx * kTileW * S - PAD;
+  const size_t plane = (size_t)Hin * Win;
+  const float* inb = in + (size_t)b * K * plane;
+
+  f32x16_t acc[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc[0][i] = 0.0f; acc[1][i] = 0.0f; }
+
+  for (int kc = 0; kc < K; kc += KC) {
+    __syncthreads();      // the previous chunk's reads are over
+    // consecutive lanes: consecutive pixels of one plane; kFillBatch loads are issued before the first one is converted
+    for (int base = tid; base < KC * PP; base += kThreads * kFillBatch) {
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, pr = rem / PW, pc = rem - pr * PW;
+        const int iy = iy0 + pr, ix = ix0 + pc;
+        v[j] = 0.0f;
+        if (idx < KC * PP && iy >= 0 && iy < Hin && ix >= 0 && ix < Win) v[j] = inb[(size_t)(kc + ch) * plane + (size_t)iy * Win + ix];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
+        if (idx >= KC * PP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(v[j], hi, lo);
+        patch[0][rem * PS + ch] = hi;
+        if constexpr (PREC == kPrecF16x3) patch[NL - 1][rem * PS + ch] = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ky = 0; ky < KS; ++ky) {
+#pragma unroll
+      for (int kx = 0; kx < KS; ++kx) {
+        const int pp = ((wave * S + ky) * PW + (l32 * S + kx)) * PS + 8 * half;
+        const size_t wrow = ((size_t)(ky * KS + kx) * N + n0 + l32) * K + kc + 8 * half;
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 16) {
+          const uint4 bh = *reinterpret_cast<const uint4*>(&patch[0][pp + kk]);
+          uint4 bl = bh;
+          if constexpr (PREC == kPrecF16x3) bl = *reinterpret_cast<const uint4*>(&patch[NL - 1][pp + kk]);
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            const size_t wo = wrow + (size_t)nb * 32 * K + kk;
+            const uint4 ah = *reinterpret_cast<const uint4*>(wh + wo);
+            uint4 al = ah;
+            if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wl + wo);
+            acc[nb] = mma_pair<PREC>(ah, al, bh, bl, acc[nb]);
+          }
+        }
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column (pixel) l % 32, row (output channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
+  const int y = ty * kTileH + wave, x = tx * kTileW + l32;
+  if (y >= Ht || x >= Wt) return;
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = n0 + nb * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      if constexpr (SCATTER) {
+        const int cout = N / 4, t4 = n / cout, co = n - t4 * cout;
+        const size_t oy = 2 * (size_t)y + (t4 >> 1), ox = 2 * (size_t)x + (t4 & 1);
+        out[(((size_t)b * cout + co) * (2 * (size_t)Ht) + oy) * (2 * (size_t)Wt) + ox] = acc[nb][r];
+      } else {
+        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = acc[nb][r];
+      }
+    }
+  }
+}
+
+// ---- weight gradient --------------------------------------------------------------------------------------------------------------------------------
+constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channels of the shifted operand in LDS: an ODD number of dwords
+  const int even = (halfs + 1) / 2 * 2;
+  return (even / 2) % 2 == 0 ? even + 2 : even;
+}
+
+// P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
+//   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
+// part [splits][Cp][Cq][KS * KS]; grid ((Cp / 64) * (Cq / 64), splits).  A pixel tile is RH rows of 32 pixels.
+template <int PREC, int KS, int S, int PAD, int RH>
+__global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __restrict__ P, const float* __restrict__ Q, float* __restrict__ part,
+                                                                 int Cp, int Cq, int Hp, int Wp, int Hq, int Wq, int tiles_x, int tiles_y,
+                                                                 long long tiles, int tiles_per_split) {
+  constexpr int T = KS * KS;
+  constexpr int QH = (RH - 1) * S + KS, QW = 31 * S + KS, QP = QH * QW, QCS = wgrad_channel_stride(QP);
+  constexpr int PP = RH * 32, PCS = PP + 8;      // a multiple of 8 halfs: the A operand's 16-byte reads are aligned
+  constexpr int NQ = 7 * S + KS;                 // values of one row of Q that the 8 pixels of a lane touch, all kx together
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  __shared__ uint16_t PL[NL][64 * PCS] __attribute__((aligned(16)));
+  __shared__ uint16_t QL[NL][64 * QCS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int nq = Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int wp = wave & 1, wq = wave >> 1;
+  const size_t plane_p = (size_t)Hp * Wp, plane_q = (size_t)Hq * Wq;
+
+  f32x16_t acc[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+  const long long t_begin = (long long)split * tiles_per_split;
+  const long long t_end = t_begin + tiles_per_split < tiles ? t_begin + tiles_per_split : tiles;
+  for (long long t = t_begin; t < t_end; ++t) {
+    const int txi = (int)(t % tiles_x), tyi = (int)((t / tiles_x) % tiles_y), b = (int)(t / ((long long)tiles_x * tiles_y));
+    const int y0 = tyi * RH, x0 = txi * 32;
+    const int qy0 = y0 * S - PAD, qx0 = x0 * S - PAD;
+    __syncthreads();      // the previous tile's reads are over
+    for (int base = tid; base < 64 * PP; base += kThreads * kFillBatch) {      // (kFillBatch loads in flight, as in the implicit GEMM)
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, y = y0 + rem / 32, x = x0 + rem % 32;
+        v[j] = 0.0f;
+        if (idx < 64 * PP && y < Hp && x < Wp) v[j] = P[((size_t)b * Cp + p0 + ch) * plane_p + (size_t)y * Wp + x];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
+        if (idx >= 64 * PP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(v[j], hi, lo);
+        PL[0][ch * PCS + rem] = hi;
+        if constexpr (PREC == kPrecF16x3) PL[NL - 1][ch * PCS + rem] = lo;
+      }
+    }
+    for (int base = tid; base < 64 * QP; base += kThreads * kFillBatch) {
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP, qr = rem / QW, y = qy0 + qr, x = qx0 + (rem - qr * QW);
+        v[j] = 0.0f;
+        if (idx < 64 * QP && y >= 0 && y < Hq && x >= 0 && x < Wq) v[j] = Q[((size_t)b * Cq + q0 + ch) * plane_q + (size_t)y * Wq + x];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP;
+        if (idx >= 64 * QP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(v[j], hi, lo);
+        QL[0][ch * QCS + rem] = hi;
+        if constexpr (PREC == kPrecF16x3) QL[NL - 1][ch * QCS + rem] = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RH; ++r) {
+#pragma unroll
+      for (int k16 = 0; k16 < 32; k16 += 16) {
+        const int po = (wp * 32 + l32) * PCS + r * 32 + k16 + 8 * half;
+        const uint4 ah = *reinterpret_cast<const uint4*>(&PL[0][po]);
+        uint4 al = ah;
+        if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(&PL[NL - 1][po]);
+#pragma unroll
+        for (int ky = 0; ky < KS; ++ky) {
+          const int qo = (wq * 32 + l32) * QCS + (r * S + ky) * QW + (k16 + 8 * half) * S;
+          uint16_t qh[NQ], ql[NQ];
+#pragma unroll
+          for (int i = 0; i < NQ; ++i) {
+            qh[i] = QL[0][qo + i];
+            ql[i] = PREC == kPrecF16x3 ? QL[NL - 1][qo + i] : (uint16_t)0;
+          }
+#pragma unroll
+          for (int kx = 0; kx < KS; ++kx) {
+            u16x8_t vh, vl;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              vh[e] = qh[e * S + kx];
+              vl[e] = ql[e * S + kx];
+            }
+            acc[ky * KS + kx] = mma_pair<PREC>(ah, al, __builtin_bit_cast(uint4, vh), __builtin_bit_cast(uint4, vl), acc[ky * KS + kx]);
+          }
+        }
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column q = l % 32, row p = 8 * (r / 4) + 4 * (l / 32) + r % 4
+  float* dst = part + (size_t)split * Cp * Cq * T;
+  const int q = q0 + wq * 32 + l32;
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int p = p0 + wp * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      dst[((size_t)p * Cq + q) * T + t] = acc[t][r];
+    }
+  }
+}
+
+// grad_w[i] = part[0][i] + part[1][i] + ... in that order
+__global__ __launch_bounds__(kThreads) void dd_conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ grad_w, size_t total,
+                                                                        int splits) {
+  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= total) return;
+  float s = part[i];
+  for (int k = 1; k < splits; ++k) s += part[(size_t)k * total + i];
+  grad_w[i] = s;
+}
+
+constexpr int kWgradRowsConv = 2, kWgradRowsDeconv = 1;      // RH of the two weight-gradient instantiations (LDS: 58.5 KB / 43.5 KB split-f16)
+
+inline unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+
+template <int PREC>
+hipError_t launch_conv_prec(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
+                            hipStream_t st) {
+  const int taps = op == kOpConv3 ? 9 : 4;
+  const size_t nw = (size_t)taps * Cin * Cout;
+  uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
+  uint16_t* wl = wh + nw;      // (only the split mode reads or writes it)
+  const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
+  const unsigned tiles = (unsigned)tiles_x * (unsigned)tiles_y;
+  if (op == kOpConv3) {
+    const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin;
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, dir == 0 ? kPackConvFwd : kPackConvBwd, N,
+                       K, 9);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 3, 1, 1, 32, false>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
+                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+  } else if (dir == 0) {
+    const int K = Cin, N = 4 * Cout;
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvFwd, N, K, 1);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 1, 1, 0, 32, true>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
+                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+  } else {
+    const int K = Cout, N = Cin;
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvBwd, N, K, 4);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 2, 2, 0, 16, false>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
+                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, 2 * H, 2 * W, H, W, tiles_x);
+  }
+  return hipGetLastError();
+}
+
+template <int PREC>
+hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                             hipStream_t st) {
+  const WgradSplit sp = wgrad_split(op, B, H, W);
+  const int tiles_x = (W + 31) / 32;
+  float* part = reinterpret_cast<float*>(workspace);
+  const dim3 grid((unsigned)((Cin / 64) * (Cout / 64)), (unsigned)sp.splits);
+  if (op == kOpConv3) {
+    const int tiles_y = (H + kWgradRowsConv - 1) / kWgradRowsConv;
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, kWgradRowsConv>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H, W, H, W,
+                       tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+  } else {
+    const int tiles_y = (H + kWgradRowsDeconv - 1) / kWgradRowsDeconv;
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, kWgradRowsDeconv>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout, H, W, 2 * H,
+                       2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+  }
+  const size_t total = (size_t)Cin * Cout * (op == kOpConv3 ? 9 : 4);
+  hipLaunchKernelGGL(dd_conv_wgrad_reduce_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+// ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
+WgradSplit wgrad_split(int op, int B, int H, int W) {
+  const int rh = op == kOpConv3 ? kWgradRowsConv : kWgradRowsDeconv;
+  WgradSplit s;
+  s.tiles = (int64_t)B * ((H + rh - 1) / rh) * ((W + 31) / 32);
+  int64_t per = (s.tiles + kMaxSplits - 1) / kMaxSplits;
+  if (per < kSplitTiles) per = kSplitTiles;
+  s.tiles_per_split = (int)per;
+  s.splits = (int)((s.tiles + per - 1) / per);
+  return s;
+}
+
+size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec) {
+  const size_t taps = op == kOpConv3 ? 9 : 4;
+  const size_t nw = taps * (size_t)Cin * (size_t)Cout;
+  const size_t packed = nw * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
+  const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * nw * sizeof(float);
+  const size_t need = packed > partials ? packed : partials;
+  return (need + 255) / 256 * 256;
+}
+
+hipError_t launch_conv(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
+                       int prec, hipStream_t st) {
+  if (prec == kPrecBf16) return launch_conv_prec<kPrecBf16>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  if (prec == kPrecF16) return launch_conv_prec<kPrecF16>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  return launch_conv_prec<kPrecF16x3>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+}
+
+hipError_t launch_wgrad(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                        int prec, hipStream_t st) {
+  if (prec == kPrecBf16) return launch_wgrad_prec<kPrecBf16>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  if (prec == kPrecF16) return launch_wgrad_prec<kPrecF16>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  return launch_wgrad_prec<kPrecF16x3>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+}
+
+}  // namespace ddconv

@@ -18,6 +18,7 @@ from torch import nn
 
 from . import modules as _modules
 from .batchnorm import convert_hip_batchnorm, resolve_bn_backend
+from .conv import convert_hip_conv, resolve_conv_backend
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
 from .necks import HAHIHeteroNeck
 from .scheduler import DDIMScheduler
@@ -50,7 +51,7 @@ class DDIMDepthEstimate_Res(nn.Module):
 
     def __init__(self, in_channels=(64, 128, 256, 512), up_scale_factor=1, inference_steps=20, num_train_timesteps=1000,
                  return_indices=None, depth_transform_cfg=None, depth_feature_dim=16, detach_fp=False, loss_cfgs=(),
-                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, **kwargs):
+                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, **kwargs):
         """Beyond the reference's keywords (src/model/diffusion_dcbase_model.py:77-91):
         profile            the two shipped configurations of a head (PROFILES below; None = $DDEPTH_PROFILE, else "reference"):
                              "reference" [default]  what the reference does, bit for bit where that is defined: fp32 arithmetic (the reference runs
@@ -72,7 +73,11 @@ class DDIMDepthEstimate_Res(nn.Module):
                            forward); "auto" = "cpu" in .train() -- the reference's training RNG stream -- and "device" in eval.
         bn_backend         "torch" [default] or "hip" (None = $DDEPTH_BN_BACKEND, else "torch"): with "hip" every BatchNorm2d of the FPN, the
                            codec and the neck becomes a batchnorm.HipBatchNorm2d holding the same tensors, its ReLU / LeakyReLU fused, so
-                           the .train() forward and backward of those layers run in csrc/dd_bn.hip (same state-dict keys; eval unchanged)"""
+                           the .train() forward and backward of those layers run in csrc/dd_bn.hip (same state-dict keys; eval unchanged)
+        conv_backend       "torch" [default] or "hip" (None = $DDEPTH_CONV_BACKEND, else "torch"): with "hip" the Conv3x3 of every conv_lateral and
+                           the ConvTranspose2d of every conv_up become conv.HipConv2d / conv.HipConvTranspose2d holding the same tensors, so
+                           their .train() forward and backward run in csrc/dd_conv.hip on `precision` operands ("bf16" / "f16" / "f16x3"; any
+                           other precision and the MPViT widths keep the torch convolutions; same state-dict keys; eval unchanged)"""
         super().__init__()
         profile = profile or os.environ.get("DDEPTH_PROFILE") or "reference"      # (an empty DDEPTH_PROFILE means "not set")
         if profile not in PROFILES:
@@ -142,6 +147,12 @@ class DDIMDepthEstimate_Res(nn.Module):
             for name in ("conv_lateral", "conv_up", "depth_transform", "hahineck", "convup_fp"):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
+        self.conv_backend = resolve_conv_backend(conv_backend)
+        if self.conv_backend == "hip":
+            # (convup_fp never runs; it is converted too, for uniformity)
+            for name in ("conv_lateral", "conv_up", "convup_fp"):
+                if hasattr(self, name):
+                    setattr(self, name, convert_hip_conv(getattr(self, name), precision))
 
     @staticmethod
     def _on_hip(tensors) -> bool:
