@@ -1,4 +1,4 @@
-"""The condition FPN's training convolutions, forward and backward, over the C ABI of include/ddepth_conv.h.
+"""The condition FPN's and the HAHI neck's training convolutions, forward and backward, over the C ABI of include/ddepth_conv.h.
 
 What it is for: in .train() the condition FPN's ``conv_lateral[i]`` (Conv3x3 C_i -> 256, no bias) and ``conv_up[j]`` (ConvTranspose2d 256 -> 256,
 k2 s2, no bias) and their autograd run as fp32 MIOpen kernels, whatever the precision of the rest of the step.  ``HipConv2d`` and
@@ -6,6 +6,12 @@ k2 s2, no bias) and their autograd run as fp32 MIOpen kernels, whatever the prec
 fp32 accumulation; only ``x`` and the weight are kept for the backward, and a gradient nobody needs is not computed.
 
     convert_hip_conv(head.conv_lateral, "bf16")      # or: DDIMDepthEstimate_Res(..., conv_backend="hip") / DDEPTH_CONV_BACKEND=hip
+
+The HAHI neck (necks.HAHIHeteroNeck) has twelve more convolutions, eight of them 1x1 (``lateral_convs``, ``conv_proj``, ``trans_proj``; no bias,
+a BatchNorm follows).  ``HipConv2d`` serves ``nn.Conv2d(cin, cout, 1, bias=False)`` too, through the pointwise kernels of the library
+(dd_conv1x1_*), but the converter replaces a 1x1 only when asked to:
+
+    convert_hip_conv(head.hahineck, "bf16", pointwise=True)      # or: conv_backend="hip+neck" / DDEPTH_CONV_BACKEND=hip+neck
 
 The library route is decided BEFORE the call and taken only when the input and the weight are contiguous fp32 tensors on a HIP device, the
 module's precision is "bf16", "f16" or "f16x3", and the channel counts are supported (multiples of 64 in 64..1536).  Everything else -- CPU
@@ -27,13 +33,15 @@ from . import backend
 
 # every symbol include/ddepth_conv.h declares (checked by tests/test_conv_cpu.py)
 ABI_SYMBOLS = ["dd_conv_last_error", "dd_conv_supported", "dd_conv_workspace_bytes", "dd_conv3x3_forward", "dd_conv3x3_backward_data",
-               "dd_conv3x3_backward_weight", "dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight"]
+               "dd_conv3x3_backward_weight", "dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight",
+               "dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight"]
 
-OP_CONV3X3, OP_DECONV2X2 = 0, 1      # dd_conv_op
+OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
 _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
 _ENTRY = {OP_CONV3X3: ("dd_conv3x3_forward", "dd_conv3x3_backward_data", "dd_conv3x3_backward_weight"),
-          OP_DECONV2X2: ("dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight")}
+          OP_DECONV2X2: ("dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight"),
+          OP_CONV1X1: ("dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight")}
 
 _bound = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
@@ -103,10 +111,10 @@ def _geometry(op: int, x: torch.Tensor, w: torch.Tensor):
     if x.dim() != 4 or w.dim() != 4:
         raise ValueError(f"expected 4D input and weight (got {x.dim()}D, {w.dim()}D)")
     B, cin, H, W = (int(s) for s in x.shape)
-    if op == OP_CONV3X3:
-        cout, wcin, k = int(w.shape[0]), int(w.shape[1]), 3
-    else:
+    if op == OP_DECONV2X2:
         wcin, cout, k = int(w.shape[0]), int(w.shape[1]), 2
+    else:
+        cout, wcin, k = int(w.shape[0]), int(w.shape[1]), 3 if op == OP_CONV3X3 else 1
     if wcin != cin or tuple(w.shape[2:]) != (k, k):
         raise ValueError(f"weight {tuple(w.shape)} does not fit input {tuple(x.shape)}")
     return B, cin, cout, H, W
@@ -127,7 +135,7 @@ def conv_forward(op: int, x: torch.Tensor, w: torch.Tensor, prec: int) -> torch.
     _check_native(w, "weight")
     dims = _geometry(op, x, w)
     B, _, cout, H, W = dims
-    s = 1 if op == OP_CONV3X3 else 2
+    s = 2 if op == OP_DECONV2X2 else 1
     return _call(op, 0, x, w, torch.empty((B, cout, s * H, s * W), dtype=torch.float32, device=x.device), dims, prec)
 
 
@@ -179,6 +187,19 @@ class Conv3x3Function(Function):
         return _backward(ctx, grad_y)
 
 
+class Conv1x1Function(Function):
+    """(x, weight, dd_precision) -> F.conv2d(x, weight) with a [Cout, Cin, 1, 1] weight over the three dd_conv1x1_* calls; as Conv3x3Function."""
+
+    @staticmethod
+    def forward(ctx, x, weight, prec):
+        return _forward(ctx, OP_CONV1X1, x, weight, prec)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        return _backward(ctx, grad_y)
+
+
 class ConvTranspose2x2Function(Function):
     """(x, weight, dd_precision) -> F.conv_transpose2d(x, weight, None, 2) over the three dd_deconv2x2_* calls; as Conv3x3Function."""
 
@@ -211,15 +232,21 @@ def _is_conv3x3(m) -> bool:
             and _pair(m.stride) == (1, 1) and m.padding != "same" and _pair(m.padding) == (1, 1))
 
 
+def _is_conv1x1(m) -> bool:
+    return (isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and _plain(m) and _pair(m.kernel_size) == (1, 1)
+            and _pair(m.stride) == (1, 1) and m.padding != "same" and _pair(m.padding) == (0, 0))
+
+
 def _is_deconv2x2(m) -> bool:
     return (isinstance(m, nn.ConvTranspose2d) and _plain(m) and _pair(m.kernel_size) == (2, 2) and _pair(m.stride) == (2, 2)
             and _pair(m.padding) == (0, 0) and _pair(m.output_padding) == (0, 0))
 
 
 class HipConv2d(nn.Conv2d):
-    """``nn.Conv2d(cin, cout, 3, 1, 1, bias=False)`` (same parameter, same state-dict key) whose forward and backward on a HIP device run in
-    csrc/dd_conv.hip on ``precision`` operands ("bf16", "f16", "f16x3"); every other precision and every tensor the library does not take
-    (module docstring) runs the inherited torch forward."""
+    """``nn.Conv2d(cin, cout, 3, 1, 1, bias=False)`` or ``nn.Conv2d(cin, cout, 1, bias=False)`` (same parameter, same state-dict key) whose
+    forward and backward on a HIP device run in csrc/dd_conv.hip on ``precision`` operands ("bf16", "f16", "f16x3"); the operator (3x3 or
+    pointwise) follows from the module's own geometry.  Every other geometry or precision and every tensor the library does not take (module
+    docstring) runs the inherited torch forward."""
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias=bias, **kwargs)
@@ -228,14 +255,19 @@ class HipConv2d(nn.Conv2d):
     def extra_repr(self):
         return super().extra_repr() + f", precision={self.precision}"
 
-    def _native(self, x) -> bool:
-        return bool(_is_conv3x3(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels
-                    and supported(OP_CONV3X3, self.in_channels, self.out_channels, self.precision))
+    def _native(self, x) -> Optional[int]:
+        """The dd_conv_op this call runs in the library, or None for the torch forward."""
+        op = OP_CONV3X3 if _is_conv3x3(self) else OP_CONV1X1 if _is_conv1x1(self) else None
+        if op is None or not (_tensors_native(x, self.weight) and x.shape[1] == self.in_channels
+                              and supported(op, self.in_channels, self.out_channels, self.precision)):
+            return None
+        return op
 
     def forward(self, x):
-        if not self._native(x):
+        op = self._native(x)
+        if op is None:
             return super().forward(x)
-        return Conv3x3Function.apply(x, self.weight, precision_id(self.precision))
+        return (Conv3x3Function if op == OP_CONV3X3 else Conv1x1Function).apply(x, self.weight, precision_id(self.precision))
 
 
 class HipConvTranspose2d(nn.ConvTranspose2d):
@@ -258,10 +290,13 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
         return ConvTranspose2x2Function.apply(x, self.weight, precision_id(self.precision))
 
 
-def eligible(m: nn.Module, precision) -> bool:
-    """3x3 s1 p1 or transpose k2 s2, no bias, groups 1, dilation 1, and channel counts and a precision dd_conv_supported accepts."""
+def eligible(m: nn.Module, precision, pointwise: bool = False) -> bool:
+    """3x3 s1 p1 or transpose k2 s2 (with ``pointwise``: or 1x1 s1 p0), no bias, groups 1, dilation 1, and channel counts and a precision
+    dd_conv_supported accepts."""
     if isinstance(m, (HipConv2d, HipConvTranspose2d)):
         return False
+    if pointwise and _is_conv1x1(m):
+        return supported(OP_CONV1X1, m.in_channels, m.out_channels, precision)
     if _is_conv3x3(m):
         return supported(OP_CONV3X3, m.in_channels, m.out_channels, precision)
     if _is_deconv2x2(m):
@@ -280,21 +315,23 @@ def _from_conv(m, precision):
     return out
 
 
-def convert_hip_conv(module: nn.Module, precision) -> nn.Module:
+def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False) -> nn.Module:
     """Every eligible convolution of ``module`` (see ``eligible``) becomes a ``HipConv2d`` / ``HipConvTranspose2d`` holding the SAME parameter
     tensor under the same name: state-dict keys and the indices inside an ``nn.Sequential`` do not change.  With a precision the library does
-    not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced."""
-    out = _from_conv(module, precision) if eligible(module, precision) else module
+    not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced.  A 1x1
+    convolution is replaced only with ``pointwise=True`` (the HAHI neck); the default leaves every 1x1 an ``nn.Conv2d``."""
+    out = _from_conv(module, precision) if eligible(module, precision, pointwise) else module
     for name, child in list(module.named_children()):
-        new = convert_hip_conv(child, precision)
+        new = convert_hip_conv(child, precision, pointwise)
         if new is not child:
             setattr(out, name, new)
     return out
 
 
 def resolve_conv_backend(conv_backend: Optional[str] = None) -> str:
-    """The head keyword ``conv_backend`` / the environment variable DDEPTH_CONV_BACKEND: "torch" (default; empty or absent) or "hip"."""
+    """The head keyword ``conv_backend`` / the environment variable DDEPTH_CONV_BACKEND: "torch" (default; empty or absent), "hip" (the FPN's
+    convolutions) or "hip+neck" (those and, on a head that has one, the HAHI neck's, its 1x1 included)."""
     choice = conv_backend or os.environ.get("DDEPTH_CONV_BACKEND") or "torch"
-    if choice not in ("torch", "hip"):
-        raise ValueError(f"conv_backend must be 'torch' or 'hip' (got {choice!r})")
+    if choice not in ("torch", "hip", "hip+neck"):
+        raise ValueError(f"conv_backend must be 'torch', 'hip' or 'hip+neck' (got {choice!r})")
     return choice

@@ -40,7 +40,7 @@ int kernel_prec(int precision) {
 
 bool channels_ok(int c) { return c >= 64 && c <= 1536 && c % 64 == 0; }
 
-bool op_ok(int op) { return op == DD_CONV_3X3 || op == DD_CONV_DECONV2X2; }
+bool op_ok(int op) { return op == DD_CONV_3X3 || op == DD_CONV_DECONV2X2 || op == DD_CONV_1X1; }
 
 // everything but the pointers; leaves the kernels' mode in *prec
 int check(int op, int B, int Cin, int Cout, int H, int W, int precision, int* prec) {
@@ -129,6 +129,21 @@ int dd_deconv2x2_backward_data(const float* grad_y, const float* w, float* grad_
 int dd_deconv2x2_backward_weight(const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H,
                                  int W, int precision, void* stream) {
   return run_wgrad(DD_CONV_DECONV2X2, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, precision, stream);
+}
+
+int dd_conv1x1_forward(const float* x, const float* w, float* y, void* workspace, int B, int Cin, int Cout, int H, int W, int precision,
+                       void* stream) {
+  return run_conv(DD_CONV_1X1, 0, x, w, y, workspace, B, Cin, Cout, H, W, precision, stream);
+}
+
+int dd_conv1x1_backward_data(const float* grad_y, const float* w, float* grad_x, void* workspace, int B, int Cin, int Cout, int H, int W,
+                             int precision, void* stream) {
+  return run_conv(DD_CONV_1X1, 1, grad_y, w, grad_x, workspace, B, Cin, Cout, H, W, precision, stream);
+}
+
+int dd_conv1x1_backward_weight(const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                               int precision, void* stream) {
+  return run_wgrad(DD_CONV_1X1, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, precision, stream);
 }
 
 }  // extern "C"

@@ -1,4 +1,4 @@
-// dd_conv.h -- launchers of csrc/dd_conv.hip (the condition FPN's training convolutions, forward and backward) for the C ABI unit
+// dd_conv.h -- launchers of csrc/dd_conv.hip (the condition FPN's and the HAHI neck's training convolutions, forward and backward) for the C ABI unit
 // csrc/dd_api_conv.cpp.  Everything is enqueued on `stream`; nothing here synchronises, allocates or reads device memory on the host.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,15 +9,17 @@
 namespace ddconv {
 
 enum { kPrecBf16 = 0, kPrecF16 = 1, kPrecF16x3 = 2 };      // operand modes of the kernels (dd_api_conv.cpp maps dd_precision onto them)
-enum { kOpConv3 = 0, kOpDeconv2 = 1 };
+enum { kOpConv3 = 0, kOpDeconv2 = 1, kOpConv1 = 2 };
 
 constexpr int kThreads = 256;            // 4 waves of 64
 constexpr int kTileH = 4, kTileW = 32;   // output pixels of one workgroup of the implicit GEMM: one 32-pixel row per wave
 constexpr int kTileN = 64;               // output channels of one workgroup
+constexpr int kPwTile = 128;             // 1x1: consecutive pixels of ONE plane a workgroup owns (32 per wave), forward, data and weight gradient alike
 constexpr int kSplitTiles = 8;           // pixel tiles one workgroup of the weight gradient adds up, at least
 constexpr int kMaxSplits = 64;           // pixel splits of the weight gradient at most (the tiles per split grow beyond)
 
-// pixel tiles of the weight gradient (32 pixels wide, rows_per_tile high) and how they are split across workgroups
+// pixel tiles of the weight gradient (32 pixels wide, rows_per_tile high; 1x1: kPwTile consecutive pixels of a plane) and how they are split
+// across workgroups
 struct WgradSplit {
   int64_t tiles;
   int tiles_per_split, splits;

@@ -1,5 +1,5 @@
-// dd_conv.hip -- the training convolutions of the condition FPN as implicit-GEMM HIP kernels for gfx950 (include/ddepth_conv.h): Conv3x3 s1 p1
-// and ConvTranspose2d k2 s2, both without bias; forward, data gradient and weight gradient.  Tensors are contiguous fp32 NCHW as torch holds
+// dd_conv.hip -- the training convolutions of the condition FPN and the HAHI neck as GEMM HIP kernels for gfx950 (include/ddepth_conv.h): Conv3x3 s1 p1,
+// ConvTranspose2d k2 s2 and the pointwise Conv1x1, all without bias; forward, data gradient and weight gradient.  Tensors are contiguous fp32 NCHW as torch holds
 // them; the operands are rounded to 16 bits on the way into LDS and contracted on v_mfma_f32_32x32x16_{bf16,f16} with fp32 accumulation.
 //
 // Structure:
@@ -17,6 +17,9 @@
 //                           pixels of a row).  A workgroup owns 64 x 64 channels and every tap, and a contiguous range of pixel tiles (a SPLIT);
 //                           it stores its partial into the workspace, and dd_conv_wgrad_reduce_kernel adds the splits in a fixed order.  No
 //                           floating-point atomics: two calls give the same bits.
+//   dd_conv1x1_gemm_kernel  the 1x1 forward / data gradient: no halo, so a workgroup owns 128 consecutive pixels of a flat plane and the pixel-side MFMA
+//   dd_conv1x1_wgrad_kernel operand comes straight from coalesced dword loads (no LDS); the 1x1 weight gradient contracts over the pixels, contiguous for
+//                           both operands, through dword LDS stores and 16-byte reads (comments at the kernels).
 //
 // Plain HIP C++ and compiler builtins; every write to memory is a plain C++ store.  Only constructs the host emulation of the tests provides.
 #include "dd_conv.h"
@@ -70,7 +73,7 @@ __device__ __forceinline__ f32x16_t mma_pair(const uint4& ah, const uint4& al, c
 }
 
 // ---- weights -> wp[tap][n][k], 16 bits ----------------------------------------------------------------------------------------------------------
-enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3 };
+enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3, kPackPwFwd = 4, kPackPwBwd = 5 };
 
 template <int PREC>
 __global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __restrict__ w, uint16_t* __restrict__ wh, uint16_t* __restrict__ wl,
@@ -87,8 +90,12 @@ __global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __r
   } else if (mode == kPackDeconvFwd) {    // n = (dy * 2 + dx) * Cout + co;  w[ci = k][co][dy][dx]
     const int cout = N / 4, t4 = n / cout, co = n - t4 * cout;
     src = ((size_t)k * cout + co) * 4 + t4;
-  } else {                                // w[ci = n][co = k][tap]
+  } else if (mode == kPackDeconvBwd) {    // w[ci = n][co = k][tap]
     src = ((size_t)n * K + k) * 4 + t;
+  } else if (mode == kPackPwFwd) {        // 1x1: w[co = n][ci = k]
+    src = (size_t)n * K + k;
+  } else {                                // 1x1 data gradient: w'[ci = n][co = k] = w[co][ci]
+    src = (size_t)k * N + n;
   }
   uint16_t hi, lo;
   to_operand<PREC>(w[src], hi, lo);
@@ -306,6 +313,147 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
   }
 }
 
+// ---- 1x1: forward and data gradient ---------------------------------------------------------------------------------------------------------------
+// out[b][n][p] = sum_k wp[n][k] . in[b][k][p] over the FLAT pixels p of a plane (P = H * W): no halo, so a workgroup owns kPwTile consecutive
+// pixels of one plane (wave w the 32 from 32 w on) and 32 * NB output channels; a tile never crosses an image, what lies behind the plane's end
+// is read as zero and not written.  Lane l of the MFMA's pixel-side operand needs channels k + 8 * (l / 32) .. + 7 of pixel l % 32: eight dword
+// loads, each one 32 consecutive floats of one plane (any P, any alignment), converted in registers and already in operand order -- no LDS and no
+// barrier in this kernel.  The weights are the A operand, 16 bytes per lane from the packed image (L1 / L2), as in the implicit GEMM.
+// grid (pixel tiles * N / (32 NB), B): the workgroups of one pixel tile are neighbours in dispatch order, so its re-reads for the other output
+// channels meet the cache.
+template <int PREC, int NB>
+__global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* __restrict__ in, const uint16_t* __restrict__ wh,
+                                                                   const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N, int P) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int nblocks = N / (32 * NB);
+  const int n0 = (int)(blockIdx.x % (unsigned)nblocks) * (32 * NB), b = blockIdx.y;
+  const int pw = (int)(blockIdx.x / (unsigned)nblocks) * kPwTile + wave * 32;      // first pixel of this wave
+  if (pw >= P) return;                                                             // (the whole wave: nothing here waits for it)
+  const int p = pw + l32;
+  const bool live = p < P;
+  const float* src = in + ((size_t)b * K + 8 * half) * (size_t)P + (live ? p : 0);
+  const uint16_t* wrow = wh + (size_t)(n0 + l32) * K + 8 * half;
+  const uint16_t* wrow_lo = wl + (size_t)(n0 + l32) * K + 8 * half;
+
+  f32x16_t acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.0f;
+
+  for (int kc = 0; kc < K; kc += 32) {      // (K is a multiple of 64) sixteen loads in flight, then two MFMA steps
+    float v[2][8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[s][e] = live ? src[(size_t)(kc + 16 * s + e) * P] : 0.0f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u16x8_t vh, vl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        uint16_t hi, lo;
+        to_operand<PREC>(v[s][e], hi, lo);
+        vh[e] = hi;
+        vl[e] = lo;
+      }
+      const uint4 bh = __builtin_bit_cast(uint4, vh), bl = __builtin_bit_cast(uint4, vl);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const size_t wo = (size_t)nb * 32 * K + kc + 16 * s;
+        const uint4 ah = *reinterpret_cast<const uint4*>(wrow + wo);
+        uint4 al = ah;
+        if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wrow_lo + wo);
+        acc[nb] = mma_pair<PREC>(ah, al, bh, bl, acc[nb]);
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column (pixel) l % 32, row (output channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
+  if (!live) return;
+  float* dst = out + ((size_t)b * N + n0 + 4 * half) * (size_t)P + p;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) dst[(size_t)(nb * 32 + 8 * (r / 4) + (r % 4)) * P] = acc[nb][r];
+}
+
+// ---- 1x1: weight gradient -----------------------------------------------------------------------------------------------------------------------------
+// part[split][cp][cq] = sum over the split's pixels of Pm[b][cp][p] . Q[b][cq][p]  (Pm = grad_y, Q = x -> grad_w[co][ci]): the contraction runs over
+// the pixels, contiguous in memory for BOTH operands and shifted for neither.  A workgroup owns 64 x 64 channels and a contiguous range of pixel
+// tiles (a SPLIT, in a fixed order), a tile being kPwTile consecutive pixels of one plane (zero behind its end).  Fill: a wave reads one channel
+// row of the tile with two dword loads per lane, pixels l and 64 + l (coalesced, any alignment), and stores them as ONE dword at slots 2 l,
+// 2 l + 1 of the channel's LDS row -- the MFMA's K runs over the slots, and both operands use the same pixel -> slot map, so the products pair up
+// the same pixels.  Dword stores of consecutive lanes to consecutive addresses, 16-byte operand reads from rows of kPwTile + 8 halfs (the four
+// 16-lane groups of a 16-byte read meet every bank once): no 2-byte scatter or gather anywhere.
+template <int PREC>
+__global__ __launch_bounds__(kThreads) void dd_conv1x1_wgrad_kernel(const float* __restrict__ Pm, const float* __restrict__ Q, float* __restrict__ part,
+                                                                    int Cp, int Cq, int P, int tiles_per_plane, long long tiles, int tiles_per_split) {
+  constexpr int RS = kPwTile + 8;      // halfs per channel row
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  constexpr int kFillChannels = kFillBatch / 2;      // channel rows a wave has in flight (two loads each)
+  __shared__ uint16_t PL[NL][64 * RS] __attribute__((aligned(16)));
+  __shared__ uint16_t QL[NL][64 * RS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int nq = Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int wp = wave & 1, wq = wave >> 1;
+
+  f32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+
+  const long long t_begin = (long long)split * tiles_per_split;
+  const long long t_end = t_begin + tiles_per_split < tiles ? t_begin + tiles_per_split : tiles;
+  for (long long t = t_begin; t < t_end; ++t) {
+    const int b = (int)(t / tiles_per_plane), px = (int)(t % tiles_per_plane) * kPwTile + lane;
+    const bool live0 = px < P, live1 = px + 64 < P;
+    __syncthreads();      // the previous tile's reads are over
+    // rows 0..63 are Pm's channels, 64..127 Q's; wave w fills rows w, w + 4, ...
+    for (int r0 = wave; r0 < 128; r0 += 4 * kFillChannels) {
+      float v[kFillChannels][2];
+#pragma unroll
+      for (int j = 0; j < kFillChannels; ++j) {
+        const int row = r0 + 4 * j;
+        const float* g = row < 64 ? Pm + ((size_t)b * Cp + p0 + row) * (size_t)P : Q + ((size_t)b * Cq + q0 + row - 64) * (size_t)P;
+        v[j][0] = live0 ? g[px] : 0.0f;
+        v[j][1] = live1 ? g[px + 64] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < kFillChannels; ++j) {
+        const int row = r0 + 4 * j;
+        uint16_t h0, l0, h1, l1;
+        to_operand<PREC>(v[j][0], h0, l0);
+        to_operand<PREC>(v[j][1], h1, l1);
+        uint16_t* dh = row < 64 ? &PL[0][row * RS] : &QL[0][(row - 64) * RS];
+        *reinterpret_cast<uint32_t*>(dh + 2 * lane) = (uint32_t)h0 | ((uint32_t)h1 << 16);
+        if constexpr (PREC == kPrecF16x3) {
+          uint16_t* dl = row < 64 ? &PL[NL - 1][row * RS] : &QL[NL - 1][(row - 64) * RS];
+          *reinterpret_cast<uint32_t*>(dl + 2 * lane) = (uint32_t)l0 | ((uint32_t)l1 << 16);
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k16 = 0; k16 < kPwTile; k16 += 16) {
+      const int po = (wp * 32 + l32) * RS + k16 + 8 * half, qo = (wq * 32 + l32) * RS + k16 + 8 * half;
+      const uint4 ah = *reinterpret_cast<const uint4*>(&PL[0][po]);
+      const uint4 bh = *reinterpret_cast<const uint4*>(&QL[0][qo]);
+      uint4 al = ah, bl = bh;
+      if constexpr (PREC == kPrecF16x3) {
+        al = *reinterpret_cast<const uint4*>(&PL[NL - 1][po]);
+        bl = *reinterpret_cast<const uint4*>(&QL[NL - 1][qo]);
+      }
+      acc = mma_pair<PREC>(ah, al, bh, bl, acc);
+    }
+  }
+
+  // accumulator entry r of lane l: column q = l % 32, row p = 8 * (r / 4) + 4 * (l / 32) + r % 4
+  float* dst = part + (size_t)split * Cp * Cq + (size_t)(p0 + wp * 32 + 4 * half) * Cq + q0 + wq * 32 + l32;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) dst[(size_t)(8 * (r / 4) + (r % 4)) * Cq] = acc[r];
+}
+
 // grad_w[i] = part[0][i] + part[1][i] + ... in that order
 __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_reduce_kernel(const float* __restrict__ part, float* __restrict__ grad_w, size_t total,
                                                                         int splits) {
@@ -323,10 +471,23 @@ inline unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kT
 template <int PREC>
 hipError_t launch_conv_prec(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
                             hipStream_t st) {
-  const int taps = op == kOpConv3 ? 9 : 4;
+  const int taps = op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1;
   const size_t nw = (size_t)taps * Cin * Cout;
   uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
   uint16_t* wl = wh + nw;      // (only the split mode reads or writes it)
+  if (op == kOpConv1) {
+    const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin, P = H * W;
+    const unsigned ptiles = (unsigned)((P + kPwTile - 1) / kPwTile);
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, dir == 0 ? kPackPwFwd : kPackPwBwd, N, K,
+                       1);
+    if (N % 128 == 0)      // four 32-channel blocks per wave where the channels allow: half the re-reads of the input
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 4>), dim3(ptiles * (unsigned)(N / 128), (unsigned)B), dim3(kThreads), 0, st, in,
+                         (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
+    else
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 2>), dim3(ptiles * (unsigned)(N / 64), (unsigned)B), dim3(kThreads), 0, st, in,
+                         (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
+    return hipGetLastError();
+  }
   const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
   const unsigned tiles = (unsigned)tiles_x * (unsigned)tiles_y;
   if (op == kOpConv3) {
@@ -356,7 +517,10 @@ hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float*
   const int tiles_x = (W + 31) / 32;
   float* part = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)((Cin / 64) * (Cout / 64)), (unsigned)sp.splits);
-  if (op == kOpConv3) {
+  if (op == kOpConv1) {
+    hipLaunchKernelGGL((dd_conv1x1_wgrad_kernel<PREC>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H * W,
+                       (H * W + kPwTile - 1) / kPwTile, (long long)sp.tiles, sp.tiles_per_split);
+  } else if (op == kOpConv3) {
     const int tiles_y = (H + kWgradRowsConv - 1) / kWgradRowsConv;
     hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, kWgradRowsConv>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H, W, H, W,
                        tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
@@ -365,7 +529,7 @@ hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float*
     hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, kWgradRowsDeconv>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout, H, W, 2 * H,
                        2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
   }
-  const size_t total = (size_t)Cin * Cout * (op == kOpConv3 ? 9 : 4);
+  const size_t total = (size_t)Cin * Cout * (op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1);
   hipLaunchKernelGGL(dd_conv_wgrad_reduce_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits);
   return hipGetLastError();
 }
@@ -376,7 +540,8 @@ hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float*
 WgradSplit wgrad_split(int op, int B, int H, int W) {
   const int rh = op == kOpConv3 ? kWgradRowsConv : kWgradRowsDeconv;
   WgradSplit s;
-  s.tiles = (int64_t)B * ((H + rh - 1) / rh) * ((W + 31) / 32);
+  if (op == kOpConv1) s.tiles = (int64_t)B * (((int64_t)H * W + kPwTile - 1) / kPwTile);      // flat tiles, none across an image
+  else s.tiles = (int64_t)B * ((H + rh - 1) / rh) * ((W + 31) / 32);
   int64_t per = (s.tiles + kMaxSplits - 1) / kMaxSplits;
   if (per < kSplitTiles) per = kSplitTiles;
   s.tiles_per_split = (int)per;
@@ -385,7 +550,7 @@ WgradSplit wgrad_split(int op, int B, int H, int W) {
 }
 
 size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec) {
-  const size_t taps = op == kOpConv3 ? 9 : 4;
+  const size_t taps = op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1;
   const size_t nw = taps * (size_t)Cin * (size_t)Cout;
   const size_t packed = nw * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
   const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * nw * sizeof(float);

@@ -77,7 +77,10 @@ class DDIMDepthEstimate_Res(nn.Module):
         conv_backend       "torch" [default] or "hip" (None = $DDEPTH_CONV_BACKEND, else "torch"): with "hip" the Conv3x3 of every conv_lateral and
                            the ConvTranspose2d of every conv_up become conv.HipConv2d / conv.HipConvTranspose2d holding the same tensors, so
                            their .train() forward and backward run in csrc/dd_conv.hip on `precision` operands ("bf16" / "f16" / "f16x3"; any
-                           other precision and the MPViT widths keep the torch convolutions; same state-dict keys; eval unchanged)"""
+                           other precision and the MPViT widths keep the torch convolutions; same state-dict keys; eval unchanged).
+                           "hip+neck" does the same and, on the HAHI heads, also converts the neck's convolutions (eight 1x1, four 3x3) with
+                           ``convert_hip_conv(self.hahineck, precision, pointwise=True)``; Swin-L's ``trans_fusion.2`` (2048 input channels,
+                           beyond the library's 1536) stays nn.Conv2d.  On a head without a neck "hip+neck" equals "hip"."""
         super().__init__()
         profile = profile or os.environ.get("DDEPTH_PROFILE") or "reference"      # (an empty DDEPTH_PROFILE means "not set")
         if profile not in PROFILES:
@@ -148,11 +151,15 @@ class DDIMDepthEstimate_Res(nn.Module):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
         self.conv_backend = resolve_conv_backend(conv_backend)
-        if self.conv_backend == "hip":
+        if self.conv_backend in ("hip", "hip+neck"):
             # (convup_fp never runs; it is converted too, for uniformity)
             for name in ("conv_lateral", "conv_up", "convup_fp"):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_conv(getattr(self, name), precision))
+        if self.conv_backend == "hip+neck" and self._HAHI:
+            # the neck's 1x1 (lateral_convs, conv_proj, trans_proj) and 3x3 (conv_fusion, trans_fusion) convolutions; what the library does not
+            # support -- Swin-L's trans_fusion.2 with 2048 input channels, most MPViT widths -- stays nn.Conv2d
+            self.hahineck = convert_hip_conv(self.hahineck, precision, pointwise=True)
 
     @staticmethod
     def _on_hip(tensors) -> bool:

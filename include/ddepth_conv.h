@@ -1,9 +1,10 @@
 /*
- * ddepth_conv.h -- C ABI of the MI355X-native training convolutions of the condition FPN, forward and backward (same shared library as
- * ddepth.h: diffusiondepth_amd/libddepth_hip.so; kernels in diffusiondepth_amd/csrc/dd_conv.hip).
+ * ddepth_conv.h -- C ABI of the MI355X-native training convolutions of the condition FPN and the HAHI neck, forward and backward (same shared
+ * library as ddepth.h: diffusiondepth_amd/libddepth_hip.so; kernels in diffusiondepth_amd/csrc/dd_conv.hip).
  *
- * What it replaces: nn.Conv2d(C_i, 256, 3, 1, 1, bias=False) (conv_lateral) and nn.ConvTranspose2d(256, 256, 2, 2, bias=False) (conv_up)
- * with their autograd in .train() -- fp32 MIOpen kernels today -- by implicit-GEMM kernels on 16-bit MFMA operands with fp32 accumulation.
+ * What it replaces: nn.Conv2d(C_i, C_o, 3, 1, 1, bias=False) (conv_lateral; the neck's conv_fusion / trans_fusion), nn.ConvTranspose2d(256, 256,
+ * 2, 2, bias=False) (conv_up) and nn.Conv2d(C_i, C_o, 1, bias=False) (the neck's lateral_convs, conv_proj, trans_proj) with their autograd in
+ * .train() -- fp32 MIOpen kernels otherwise -- by GEMM kernels on 16-bit MFMA operands with fp32 accumulation.
  *
  * Conventions (those of ddepth_bn.h): DEVICE pointers; every tensor is contiguous fp32 NCHW exactly as torch holds it, the weights are the
  * raw parameters (nothing is cached across calls); inputs are borrowed, outputs are caller-allocated and may not alias an input; work is
@@ -30,7 +31,8 @@ extern "C" {
 
 typedef enum dd_conv_op {
   DD_CONV_3X3 = 0,        /* Conv2d k3 s1 p1, no bias */
-  DD_CONV_DECONV2X2 = 1   /* ConvTranspose2d k2 s2, no bias */
+  DD_CONV_DECONV2X2 = 1,  /* ConvTranspose2d k2 s2, no bias */
+  DD_CONV_1X1 = 2         /* Conv2d k1 s1 p0 (pointwise), no bias */
 } dd_conv_op;
 
 /* Message of the last failing call of this header on the calling thread.  Never NULL. */
@@ -58,6 +60,15 @@ int dd_deconv2x2_backward_data(const float* grad_y, const float* w, float* grad_
                                int precision, void* stream);
 int dd_deconv2x2_backward_weight(const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H,
                                  int W, int precision, void* stream);
+
+/* 1x1 (pointwise), stride 1, no padding, no bias:  x[B,Cin,H,W], w[Cout,Cin,1,1], y[B,Cout,H,W].  Kernels of their own: a plane is a flat run of
+ * H * W pixels (no halo), tiled 128 consecutive pixels at a time; any H * W, odd ones included (every load of a tensor is a dword load). */
+int dd_conv1x1_forward(const float* x, const float* w, float* y, void* workspace, int B, int Cin, int Cout, int H, int W, int precision,
+                       void* stream);
+int dd_conv1x1_backward_data(const float* grad_y, const float* w, float* grad_x, void* workspace, int B, int Cin, int Cout, int H, int W,
+                             int precision, void* stream);
+int dd_conv1x1_backward_weight(const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                               int precision, void* stream);
 
 #ifdef __cplusplus
 }
