@@ -27,6 +27,7 @@ from .metric import Diffusion_DCbase_Metric, MetricAccumulator
 from .loss import Diffusion_DCbase_Loss
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
 from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv
+from .codec import HipCodecConv2d, HipCodecConvTranspose2d, HipCodecTail, convert_hip_codec
 
 __all__ = [
     "DDIMScheduler", "HipDenoiser", "precision_id", "library_path", "load_library",
@@ -35,5 +36,6 @@ __all__ = [
     "DDIMDepthEstimate_ResVis", "DDIMDepthEstimate_Swin_ADDHAHIVis", "HAHIHeteroNeck", "NLSPN", "Diffusion_DCbase_Model",
     "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
     "HipBatchNorm2d", "convert_hip_batchnorm", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
+    "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec",
 ]
 __version__ = "0.1.0"

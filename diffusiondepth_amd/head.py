@@ -18,6 +18,7 @@ from torch import nn
 
 from . import modules as _modules
 from .batchnorm import convert_hip_batchnorm, resolve_bn_backend
+from .codec import convert_hip_codec, resolve_codec_backend
 from .conv import convert_hip_conv, resolve_conv_backend
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
 from .necks import HAHIHeteroNeck
@@ -51,7 +52,7 @@ class DDIMDepthEstimate_Res(nn.Module):
 
     def __init__(self, in_channels=(64, 128, 256, 512), up_scale_factor=1, inference_steps=20, num_train_timesteps=1000,
                  return_indices=None, depth_transform_cfg=None, depth_feature_dim=16, detach_fp=False, loss_cfgs=(),
-                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, **kwargs):
+                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, codec_backend=None, **kwargs):
         """Beyond the reference's keywords (src/model/diffusion_dcbase_model.py:77-91):
         profile            the two shipped configurations of a head (PROFILES below; None = $DDEPTH_PROFILE, else "reference"):
                              "reference" [default]  what the reference does, bit for bit where that is defined: fp32 arithmetic (the reference runs
@@ -80,7 +81,11 @@ class DDIMDepthEstimate_Res(nn.Module):
                            other precision and the MPViT widths keep the torch convolutions; same state-dict keys; eval unchanged).
                            "hip+neck" does the same and, on the HAHI heads, also converts the neck's convolutions (eight 1x1, four 3x3) with
                            ``convert_hip_conv(self.hahineck, precision, pointwise=True)``; Swin-L's ``trans_fusion.2`` (2048 input channels,
-                           beyond the library's 1536) stays nn.Conv2d.  On a head without a neck "hip+neck" equals "hip"."""
+                           beyond the library's 1536) stays nn.Conv2d.  On a head without a neck "hip+neck" equals "hip".
+        codec_backend      "torch" [default] or "hip" (None = $DDEPTH_CODEC_BACKEND, else "torch"): with "hip" the four convolutions of
+                           ``depth_transform`` become codec.HipCodecConv2d / codec.HipCodecConvTranspose2d holding the same tensors and the
+                           decoder's nn.Sigmoid a codec.HipCodecTail, so their .train() forward and backward run in csrc/dd_codec.hip in
+                           fp32, whatever `precision` is (same state-dict keys; the eval-mode dd_encode / dd_decode unchanged)."""
         super().__init__()
         profile = profile or os.environ.get("DDEPTH_PROFILE") or "reference"      # (an empty DDEPTH_PROFILE means "not set")
         if profile not in PROFILES:
@@ -156,6 +161,9 @@ class DDIMDepthEstimate_Res(nn.Module):
             for name in ("conv_lateral", "conv_up", "convup_fp"):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_conv(getattr(self, name), precision))
+        self.codec_backend = resolve_codec_backend(codec_backend)
+        if self.codec_backend == "hip":
+            convert_hip_codec(self.depth_transform)
         if self.conv_backend == "hip+neck" and self._HAHI:
             # the neck's 1x1 (lateral_convs, conv_proj, trans_proj) and 3x3 (conv_fusion, trans_fusion) convolutions; what the library does not
             # support -- Swin-L's trans_fusion.2 with 2048 input channels, most MPViT widths -- stays nn.Conv2d

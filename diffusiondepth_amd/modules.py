@@ -19,6 +19,7 @@ from torch import nn
 import torch.nn.functional as F
 
 from .backend import HipDenoiser
+from .codec import HipCodecTail
 from .scheduler import DDIMScheduler
 
 DEFAULT_PRECISION = os.environ.get("DDEPTH_PRECISION", "fp32")
@@ -465,7 +466,10 @@ def _conv_bn_relu(ch_in, ch_out, kernel, stride=1, padding=0, bn=True, relu=True
 class DeepDepthTransformWithUpsampling(nn.Module):
     """Latent encoder t() / decoder inv_t() (reference depth_transform.py:10-35).  Eval-mode BatchNorm (running statistics)
     is what the HIP kernels implement; in .train() mode (batch statistics, autograd into the codec weights) the same torch
-    modules run in PyTorch-ROCm -- the codec is ~1 GFLOP per image."""
+    modules run in PyTorch-ROCm -- the codec is ~1 GFLOP per image.
+
+    After ``codec.convert_hip_codec`` the last child of ``conv_inv_transform`` is a ``codec.HipCodecTail``, which returns the DEPTH (not the
+    sigmoid) for a contiguous fp32 tensor on a HIP device: call ``inv_t``, never ``conv_inv_transform(x)`` directly, on a converted codec."""
 
     def __init__(self, hidden: int = 16, eps: float = 1e-6, bound: Optional[HipBound] = None):
         super().__init__()
@@ -491,5 +495,13 @@ class DeepDepthTransformWithUpsampling(nn.Module):
 
     def inv_t(self, value):
         if self._torch_path(value):
+            tail = self.conv_inv_transform[-1]
+            if isinstance(tail, HipCodecTail):                                       # (codec.convert_hip_codec)
+                z = value
+                for layer in list(self.conv_inv_transform)[:-1]:
+                    z = layer(z)
+                if tail.returns_depth(z):                                            # decided before the call: the fused tail IS the depth
+                    return tail(z)
+                return 1.0 / tail(z).clamp(self.eps) - 1
             return 1.0 / self.conv_inv_transform(value).clamp(self.eps) - 1          # depth_transform.py:33-35
         return self.bound.ensure(value.device, need=("codec",)).decode(value.float())
