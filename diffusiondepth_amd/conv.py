@@ -14,7 +14,8 @@ a BatchNorm follows).  ``HipConv2d`` serves ``nn.Conv2d(cin, cout, 1, bias=False
     convert_hip_conv(head.hahineck, "bf16", pointwise=True)      # or: conv_backend="hip+neck" / DDEPTH_CONV_BACKEND=hip+neck
 
 The library route is decided BEFORE the call and taken only when the input and the weight are contiguous fp32 tensors on a HIP device, the
-module's precision is "bf16", "f16" or "f16x3", and the channel counts are supported (multiples of 64 in 64..1536).  Everything else -- CPU
+module's precision is "bf16", "f16" or "f16x3", and the channel counts are supported: multiples of 64 in 64..1536, or, for a module converted
+with ``channels="any"`` (``conv_backend="hip+all"``), multiples of 8 in 8..2048 through dd_convx_*.  Everything else -- CPU
 tensors, the "fp32" / "f16r" / "naive_fp32" precisions, other dtypes or layouts -- calls the torch forward the module inherits.  It is never a
 fallback after an error, nothing is copied or converted silently, and there is no CPU library path.
 """
@@ -34,7 +35,8 @@ from . import backend
 # every symbol include/ddepth_conv.h declares (checked by tests/test_conv_cpu.py)
 ABI_SYMBOLS = ["dd_conv_last_error", "dd_conv_supported", "dd_conv_workspace_bytes", "dd_conv3x3_forward", "dd_conv3x3_backward_data",
                "dd_conv3x3_backward_weight", "dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight",
-               "dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight"]
+               "dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight",
+               "dd_convx_supported", "dd_convx_workspace_bytes", "dd_convx_forward", "dd_convx_backward_data", "dd_convx_backward_weight"]
 
 OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
@@ -42,6 +44,10 @@ _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS
 _ENTRY = {OP_CONV3X3: ("dd_conv3x3_forward", "dd_conv3x3_backward_data", "dd_conv3x3_backward_weight"),
           OP_DECONV2X2: ("dd_deconv2x2_forward", "dd_deconv2x2_backward_data", "dd_deconv2x2_backward_weight"),
           OP_CONV1X1: ("dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight")}
+_ENTRY_ANY = ("dd_convx_forward", "dd_convx_backward_data", "dd_convx_backward_weight")      # (op, ...): the extended channel range
+# the channel contracts: "block64" = multiples of 64 in 64..1536 (dd_conv_*), "any" = multiples of 8 in 8..2048 (dd_convx_*, a superset that
+# runs a block-64 shape through the same kernels)
+CHANNELS = ("block64", "any")
 
 _bound = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
@@ -60,6 +66,12 @@ def _lib():
             for n in names:
                 f = getattr(lib, n)
                 f.restype, f.argtypes = c_int, [c_vp] * 4 + [c_int] * 6 + [c_vp]
+        lib.dd_convx_supported.restype, lib.dd_convx_supported.argtypes = c_int, [c_int] * 4
+        lib.dd_convx_workspace_bytes.restype = c_int
+        lib.dd_convx_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+        for n in _ENTRY_ANY:
+            f = getattr(lib, n)
+            f.restype, f.argtypes = c_int, [c_int] + [c_vp] * 4 + [c_int] * 6 + [c_vp]
         _bound = lib
     return _bound
 
@@ -79,18 +91,28 @@ def precision_id(precision) -> Optional[int]:
     return pid if pid in _LIBRARY_PRECISION_IDS else None
 
 
-def supported(op: int, cin: int, cout: int, precision) -> bool:
-    """dd_conv_supported: no device needed, no side effects."""
+def _any(channels) -> bool:
+    if channels not in CHANNELS:
+        raise ValueError(f"channels must be 'block64' or 'any' (got {channels!r})")
+    return channels == "any"
+
+
+def supported(op: int, cin: int, cout: int, precision, channels="block64") -> bool:
+    """dd_conv_supported, or with ``channels="any"`` dd_convx_supported: no device needed, no side effects."""
     p = precision_id(precision)
-    return p is not None and bool(_lib().dd_conv_supported(int(op), int(cin), int(cout), p))
+    query = _lib().dd_convx_supported if _any(channels) else _lib().dd_conv_supported
+    return p is not None and bool(query(int(op), int(cin), int(cout), p))
 
 
-def workspace_for(t: torch.Tensor, op: int, B: int, cin: int, cout: int, H: int, W: int, prec: int) -> torch.Tensor:
+def workspace_for(t: torch.Tensor, op: int, B: int, cin: int, cout: int, H: int, W: int, prec: int, channels="block64") -> torch.Tensor:
     """The device scratch of one call (packed 16-bit weights, or the weight gradient's partial sums), cached per (device, bytes): a shape that
     returns finds its buffer again, and the steady state allocates nothing.  Calls on one stream are ordered, so sites of equal size share a
     buffer.  A first call inside a graph capture would allocate from the capture's pool: call once eagerly before capturing."""
     need = ctypes.c_int64(0)
-    _ck(_lib().dd_conv_workspace_bytes(op, B, cin, cout, H, W, prec, ctypes.byref(need)), "dd_conv_workspace_bytes")
+    if _any(channels):
+        _ck(_lib().dd_convx_workspace_bytes(op, B, cin, cout, H, W, prec, ctypes.byref(need)), "dd_convx_workspace_bytes")
+    else:
+        _ck(_lib().dd_conv_workspace_bytes(op, B, cin, cout, H, W, prec, ctypes.byref(need)), "dd_conv_workspace_bytes")
     key = (t.device.index if t.device.index is not None else torch.cuda.current_device(), int(need.value))
     ws = _workspaces.get(key)
     if ws is None:
@@ -120,66 +142,78 @@ def _geometry(op: int, x: torch.Tensor, w: torch.Tensor):
     return B, cin, cout, H, W
 
 
-def _call(op, which, a, b, out, dims, prec):
+def _call(op, which, a, b, out, dims, prec, channels):
     B, cin, cout, H, W = dims
     with torch.cuda.device(a.device):
-        ws = workspace_for(a, op, B, cin, cout, H, W, prec)
-        name = _ENTRY[op][which]
-        _ck(getattr(_lib(), name)(a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, prec, _stream(a)), name)
+        ws = workspace_for(a, op, B, cin, cout, H, W, prec, channels)
+        args = (a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, prec, _stream(a))
+        if _any(channels):
+            name = _ENTRY_ANY[which]
+            _ck(getattr(_lib(), name)(op, *args), name)
+        else:
+            name = _ENTRY[op][which]
+            _ck(getattr(_lib(), name)(*args), name)
     return out
 
 
 # ---- the three directions, one function each (what the tests and tools drive; the autograd Function below is built from them) -----------------
-def conv_forward(op: int, x: torch.Tensor, w: torch.Tensor, prec: int) -> torch.Tensor:
+def conv_forward(op: int, x: torch.Tensor, w: torch.Tensor, prec: int, channels="block64") -> torch.Tensor:
+    _any(channels)      # (a wrong value is an error before anything else)
     _check_native(x, "x")
     _check_native(w, "weight")
     dims = _geometry(op, x, w)
     B, _, cout, H, W = dims
     s = 2 if op == OP_DECONV2X2 else 1
-    return _call(op, 0, x, w, torch.empty((B, cout, s * H, s * W), dtype=torch.float32, device=x.device), dims, prec)
+    return _call(op, 0, x, w, torch.empty((B, cout, s * H, s * W), dtype=torch.float32, device=x.device), dims, prec, channels)
 
 
-def conv_backward_data(op: int, grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int) -> torch.Tensor:
+def conv_backward_data(op: int, grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int, channels="block64") -> torch.Tensor:
+    _any(channels)      # (a wrong value is an error before anything else)
     _check_native(grad_y, "grad_y")
     _check_native(w, "weight")
     grad_x = torch.empty(tuple(x_shape), dtype=torch.float32, device=grad_y.device)
-    return _call(op, 1, grad_y, w, grad_x, _geometry(op, grad_x, w), prec)
+    return _call(op, 1, grad_y, w, grad_x, _geometry(op, grad_x, w), prec, channels)
 
 
-def conv_backward_weight(op: int, x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int) -> torch.Tensor:
+def conv_backward_weight(op: int, x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int, channels="block64") -> torch.Tensor:
+    _any(channels)      # (a wrong value is an error before anything else)
     _check_native(x, "x")
     _check_native(grad_y, "grad_y")
     grad_w = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
-    return _call(op, 2, x, grad_y, grad_w, _geometry(op, x, grad_w), prec)
+    return _call(op, 2, x, grad_y, grad_w, _geometry(op, x, grad_w), prec, channels)
 
 
-def _forward(ctx, op, x, weight, prec):
+def _forward(ctx, op, x, weight, prec, channels):
     ctx.save_for_backward(x, weight)
-    ctx.conf = (int(op), int(prec))
-    return conv_forward(op, x, weight.detach(), int(prec))
+    ctx.conf = (int(op), int(prec), channels)
+    # (positional, and the default contract with exactly the arguments it always had: callers wrap these three functions)
+    extra = (channels,) if _any(channels) else ()
+    return conv_forward(op, x, weight.detach(), int(prec), *extra)
 
 
 def _backward(ctx, grad_y):
     x, weight = ctx.saved_tensors
-    op, prec = ctx.conf
+    op, prec, channels = ctx.conf
+    extra = (channels,) if _any(channels) else ()
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     if not (need_x or need_w):
-        return None, None, None
+        return None, None, None, None
     gy = grad_y.detach()
     if gy.dtype != torch.float32 or not gy.is_contiguous():
         gy = gy.float().contiguous()
-    gx = conv_backward_data(op, gy, weight.detach(), x.shape, prec) if need_x else None      # not for a detached input
-    gw = conv_backward_weight(op, x, gy, weight.shape, prec) if need_w else None             # not for a frozen weight
-    return gx, gw, None
+    gx = conv_backward_data(op, gy, weight.detach(), x.shape, prec, *extra) if need_x else None      # not for a detached input
+    gw = conv_backward_weight(op, x, gy, weight.shape, prec, *extra) if need_w else None             # not for a frozen weight
+    return gx, gw, None, None
 
 
 class Conv3x3Function(Function):
-    """(x, weight, dd_precision) -> F.conv2d(x, weight, None, 1, 1) over the three dd_conv3x3_* calls.  Kept for the backward: x and weight.  A
-    gradient ``ctx.needs_input_grad`` does not ask for is not computed.  Nothing synchronises the host."""
+    """(x, weight, dd_precision[, channels]) -> F.conv2d(x, weight, None, 1, 1) over the three dd_conv3x3_* calls (``channels="any"``: over
+    dd_convx_*; the choice travels in ``ctx.conf``).  Kept for the backward: x and weight.  A gradient ``ctx.needs_input_grad`` does not ask for
+    is not computed.  Nothing synchronises the host."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec):
-        return _forward(ctx, OP_CONV3X3, x, weight, prec)
+    def forward(ctx, x, weight, prec, channels="block64"):
+        return _forward(ctx, OP_CONV3X3, x, weight, prec, channels)
 
     @staticmethod
     @once_differentiable
@@ -191,8 +225,8 @@ class Conv1x1Function(Function):
     """(x, weight, dd_precision) -> F.conv2d(x, weight) with a [Cout, Cin, 1, 1] weight over the three dd_conv1x1_* calls; as Conv3x3Function."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec):
-        return _forward(ctx, OP_CONV1X1, x, weight, prec)
+    def forward(ctx, x, weight, prec, channels="block64"):
+        return _forward(ctx, OP_CONV1X1, x, weight, prec, channels)
 
     @staticmethod
     @once_differentiable
@@ -204,8 +238,8 @@ class ConvTranspose2x2Function(Function):
     """(x, weight, dd_precision) -> F.conv_transpose2d(x, weight, None, 2) over the three dd_deconv2x2_* calls; as Conv3x3Function."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec):
-        return _forward(ctx, OP_DECONV2X2, x, weight, prec)
+    def forward(ctx, x, weight, prec, channels="block64"):
+        return _forward(ctx, OP_DECONV2X2, x, weight, prec, channels)
 
     @staticmethod
     @once_differentiable
@@ -242,24 +276,30 @@ def _is_deconv2x2(m) -> bool:
             and _pair(m.padding) == (0, 0) and _pair(m.output_padding) == (0, 0))
 
 
+def _channels_repr(channels) -> str:
+    return "" if channels == "block64" else f", channels={channels}"
+
+
 class HipConv2d(nn.Conv2d):
     """``nn.Conv2d(cin, cout, 3, 1, 1, bias=False)`` or ``nn.Conv2d(cin, cout, 1, bias=False)`` (same parameter, same state-dict key) whose
     forward and backward on a HIP device run in csrc/dd_conv.hip on ``precision`` operands ("bf16", "f16", "f16x3"); the operator (3x3 or
     pointwise) follows from the module's own geometry.  Every other geometry or precision and every tensor the library does not take (module
     docstring) runs the inherited torch forward."""
 
+    channels = "block64"      # the channel contract (CHANNELS); a class attribute, so modules made before it existed behave as they did
+
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias=bias, **kwargs)
         self.precision = precision
 
     def extra_repr(self):
-        return super().extra_repr() + f", precision={self.precision}"
+        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels)
 
     def _native(self, x) -> Optional[int]:
         """The dd_conv_op this call runs in the library, or None for the torch forward."""
         op = OP_CONV3X3 if _is_conv3x3(self) else OP_CONV1X1 if _is_conv1x1(self) else None
         if op is None or not (_tensors_native(x, self.weight) and x.shape[1] == self.in_channels
-                              and supported(op, self.in_channels, self.out_channels, self.precision)):
+                              and supported(op, self.in_channels, self.out_channels, self.precision, self.channels)):
             return None
         return op
 
@@ -267,44 +307,46 @@ class HipConv2d(nn.Conv2d):
         op = self._native(x)
         if op is None:
             return super().forward(x)
-        return (Conv3x3Function if op == OP_CONV3X3 else Conv1x1Function).apply(x, self.weight, precision_id(self.precision))
+        return (Conv3x3Function if op == OP_CONV3X3 else Conv1x1Function).apply(x, self.weight, precision_id(self.precision), self.channels)
 
 
 class HipConvTranspose2d(nn.ConvTranspose2d):
     """``nn.ConvTranspose2d(cin, cout, 2, 2, bias=False)``; as HipConv2d."""
+
+    channels = "block64"
 
     def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, padding=0, output_padding=0, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, output_padding, bias=bias, **kwargs)
         self.precision = precision
 
     def extra_repr(self):
-        return super().extra_repr() + f", precision={self.precision}"
+        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels)
 
     def _native(self, x, output_size) -> bool:
         return bool(output_size is None and _is_deconv2x2(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels
-                    and supported(OP_DECONV2X2, self.in_channels, self.out_channels, self.precision))
+                    and supported(OP_DECONV2X2, self.in_channels, self.out_channels, self.precision, self.channels))
 
     def forward(self, x, output_size=None):
         if not self._native(x, output_size):
             return super().forward(x, output_size)
-        return ConvTranspose2x2Function.apply(x, self.weight, precision_id(self.precision))
+        return ConvTranspose2x2Function.apply(x, self.weight, precision_id(self.precision), self.channels)
 
 
-def eligible(m: nn.Module, precision, pointwise: bool = False) -> bool:
+def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64") -> bool:
     """3x3 s1 p1 or transpose k2 s2 (with ``pointwise``: or 1x1 s1 p0), no bias, groups 1, dilation 1, and channel counts and a precision
-    dd_conv_supported accepts."""
+    dd_conv_supported (``channels="any"``: dd_convx_supported) accepts."""
     if isinstance(m, (HipConv2d, HipConvTranspose2d)):
         return False
     if pointwise and _is_conv1x1(m):
-        return supported(OP_CONV1X1, m.in_channels, m.out_channels, precision)
+        return supported(OP_CONV1X1, m.in_channels, m.out_channels, precision, channels)
     if _is_conv3x3(m):
-        return supported(OP_CONV3X3, m.in_channels, m.out_channels, precision)
+        return supported(OP_CONV3X3, m.in_channels, m.out_channels, precision, channels)
     if _is_deconv2x2(m):
-        return supported(OP_DECONV2X2, m.in_channels, m.out_channels, precision)
+        return supported(OP_DECONV2X2, m.in_channels, m.out_channels, precision, channels)
     return False
 
 
-def _from_conv(m, precision):
+def _from_conv(m, precision, channels="block64"):
     cls = HipConvTranspose2d if isinstance(m, nn.ConvTranspose2d) else HipConv2d
     out = cls.__new__(cls)
     nn.Module.__init__(out)
@@ -312,17 +354,21 @@ def _from_conv(m, precision):
     out._parameters.update(m._parameters)      # the SAME tensors: optimizers built before the conversion stay valid
     out._buffers.update(m._buffers)
     out.precision = precision
+    if channels != "block64":      # (the default stays the class attribute)
+        out.channels = channels
     return out
 
 
-def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False) -> nn.Module:
+def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False, channels="block64") -> nn.Module:
     """Every eligible convolution of ``module`` (see ``eligible``) becomes a ``HipConv2d`` / ``HipConvTranspose2d`` holding the SAME parameter
     tensor under the same name: state-dict keys and the indices inside an ``nn.Sequential`` do not change.  With a precision the library does
     not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced.  A 1x1
-    convolution is replaced only with ``pointwise=True`` (the HAHI neck); the default leaves every 1x1 an ``nn.Conv2d``."""
-    out = _from_conv(module, precision) if eligible(module, precision, pointwise) else module
+    convolution is replaced only with ``pointwise=True`` (the HAHI neck); the default leaves every 1x1 an ``nn.Conv2d``.  ``channels="any"``
+    takes every multiple of 8 in 8..2048 (MPViT's 216 / 288, Swin-L's 2048 -> 1536) and marks the new modules with it; the default keeps
+    the block-64 contract, multiples of 64 in 64..1536."""
+    out = _from_conv(module, precision, channels) if eligible(module, precision, pointwise, channels) else module
     for name, child in list(module.named_children()):
-        new = convert_hip_conv(child, precision, pointwise)
+        new = convert_hip_conv(child, precision, pointwise, channels)
         if new is not child:
             setattr(out, name, new)
     return out
@@ -330,8 +376,9 @@ def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False) -> n
 
 def resolve_conv_backend(conv_backend: Optional[str] = None) -> str:
     """The head keyword ``conv_backend`` / the environment variable DDEPTH_CONV_BACKEND: "torch" (default; empty or absent), "hip" (the FPN's
-    convolutions) or "hip+neck" (those and, on a head that has one, the HAHI neck's, its 1x1 included)."""
+    convolutions), "hip+neck" (those and, on a head that has one, the HAHI neck's, its 1x1 included) or "hip+all" (as "hip+neck", with the
+    extended channel range: every FPN and neck convolution of every registered head)."""
     choice = conv_backend or os.environ.get("DDEPTH_CONV_BACKEND") or "torch"
-    if choice not in ("torch", "hip", "hip+neck"):
-        raise ValueError(f"conv_backend must be 'torch', 'hip' or 'hip+neck' (got {choice!r})")
+    if choice not in ("torch", "hip", "hip+neck", "hip+all"):
+        raise ValueError(f"conv_backend must be 'torch', 'hip', 'hip+neck' or 'hip+all' (got {choice!r})")
     return choice

@@ -26,7 +26,18 @@ struct WgradSplit {
 };
 WgradSplit wgrad_split(int op, int B, int H, int W);
 
-// bytes of workspace one shape needs: the packed 16-bit weights of forward / data gradient, or the weight gradient's partials
+// Channel counts.  The block-64 contract (multiples of 64 in 64..1536) runs the unguarded instantiations; every other pair of multiples of 8 in
+// 8..2048 (the extended contract of dd_convx_*, checked in dd_api_conv.cpp) runs the guarded ("ragged") ones, which fill channels beyond the
+// count as zeros, store only real rows, and read a weight image padded to whole tiles.  launch_conv / launch_wgrad choose by the shape alone.
+bool block64(int Cin, int Cout);
+
+// halfs of the packed weight image of one direction (dir as in launch_conv): taps * (N rounded up to kTileN) * (K rounded up to the GEMM's K
+// step); taps * Cin * Cout for block-64 counts
+size_t packed_halfs(int op, int dir, int Cin, int Cout);
+
+// bytes of workspace one shape needs: the larger packed 16-bit weight image of forward / data gradient (padded, see packed_halfs; twice in the
+// split mode), or the weight gradient's partials [splits][taps * Cin * Cout] fp32.  The partials grow with the channel range: the 3x3 weight
+// gradient of 2048 -> 1536 at the KITTI level-3 geometry (B = 4, 11 x 38) takes 6 splits of 113 MB, about 680 MB.
 size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec);
 
 // dir: 0 forward, 1 data gradient.  `in` / `out` are x / y (forward) or grad_y / grad_x (data gradient); H, W = input size of the forward.

@@ -33,6 +33,8 @@ typedef __attribute__((ext_vector_type(8))) _Float16 f16x8_t;
 typedef __attribute__((ext_vector_type(8))) uint16_t u16x8_t;
 typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
+__host__ __device__ constexpr int padded(int n, int step) { return (n + step - 1) / step * step; }
+
 constexpr int kFillBatch = 8;      // global loads a thread has in flight while it fills LDS (one wave per SIMD cannot hide them otherwise)
 
 __device__ __forceinline__ uint16_t f32_to_bf16(float f) {      // round to nearest even
@@ -75,13 +77,24 @@ __device__ __forceinline__ f32x16_t mma_pair(const uint4& ah, const uint4& al, c
 // ---- weights -> wp[tap][n][k], 16 bits ----------------------------------------------------------------------------------------------------------
 enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3, kPackPwFwd = 4, kPackPwBwd = 5 };
 
-template <int PREC>
+// RAGGED: the image is wp[tap][Np][Kp] with Np = N rounded up to kTileN and Kp = K rounded up to the GEMM's K step `kstep`; every element of it is
+// written on every call, zero where n >= N or k >= K (the workspace arrives with arbitrary contents), so every 16-byte read of the GEMM kernels
+// is aligned, inside the image, and meets zeros in the pad.  `wl` starts taps * Np * Kp halfs behind `wh`.
+template <int PREC, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __restrict__ w, uint16_t* __restrict__ wh, uint16_t* __restrict__ wl,
-                                                                int mode, int N, int K, int taps) {
-  const size_t total = (size_t)taps * N * K;
+                                                                int mode, int N, int K, int taps, int kstep) {
+  const int Kp = RAGGED ? padded(K, kstep) : K, Np = RAGGED ? padded(N, kTileN) : N;
+  const size_t total = (size_t)taps * Np * Kp;
   const size_t idx = (size_t)blockIdx.x * kThreads + threadIdx.x;
   if (idx >= total) return;
-  const int k = (int)(idx % K), n = (int)((idx / K) % N), t = (int)(idx / ((size_t)K * N));
+  const int k = (int)(idx % Kp), n = (int)((idx / Kp) % Np), t = (int)(idx / ((size_t)Kp * Np));
+  if constexpr (RAGGED) {
+    if (n >= N || k >= K) {
+      wh[idx] = 0;
+      if constexpr (PREC == kPrecF16x3) wl[idx] = 0;
+      return;
+    }
+  }
   size_t src;
   if (mode == kPackConvFwd) {             // w[co = n][ci = k][tap]
     src = ((size_t)n * K + k) * 9 + t;
@@ -107,7 +120,9 @@ __global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __r
 // in [B][K][Hin][Win], wp [KS * KS][N][K]; grid (tiles, N / 64, B).  The tile grid is Ht x Wt pixels:
 //   !SCATTER: out [B][N][Ht][Wt], pixel (y, x) of the tile grid reads input pixels (y * S - PAD + ky, x * S - PAD + kx)
 //   SCATTER:  out [B][N / 4][2 Ht][2 Wt], GEMM column n = (dy * 2 + dx) * (N / 4) + co goes to pixel (2y + dy, 2x + dx) of plane co
-template <int PREC, int KS, int S, int PAD, int KC, bool SCATTER>
+// RAGGED (K, N multiples of 8, not of the tiles): the weight image is the padded one of the pack kernel, channels >= K are filled as zeros, rows
+// >= N are not stored, and grid y is ceil(N / 64).  The K chunks and their order are those of the block-64 instantiation.
+template <int PREC, int KS, int S, int PAD, int KC, bool SCATTER, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __restrict__ in, const uint16_t* __restrict__ wh,
                                                                  const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N,
                                                                  int Hin, int Win, int Ht, int Wt, int tiles_x) {
@@ -121,6 +136,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __
   const int iy0 = ty * kTileH * S - PAD, ix0 = tx * kTileW * S - PAD;
   const size_t plane = (size_t)Hin * Win;
   const float* inb = in + (size_t)b * K * plane;
+  const int Kp = RAGGED ? padded(K, KC) : K, Np = RAGGED ? padded(N, kTileN) : N;      // the weight image's row length and rows per tap
 
   f32x16_t acc[2];
 #pragma unroll
@@ -136,7 +152,8 @@ __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __
         const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, pr = rem / PW, pc = rem - pr * PW;
         const int iy = iy0 + pr, ix = ix0 + pc;
         v[j] = 0.0f;
-        if (idx < KC * PP && iy >= 0 && iy < Hin && ix >= 0 && ix < Win) v[j] = inb[(size_t)(kc + ch) * plane + (size_t)iy * Win + ix];
+        if (idx < KC * PP && (!RAGGED || kc + ch < K) && iy >= 0 && iy < Hin && ix >= 0 && ix < Win)
+          v[j] = inb[(size_t)(kc + ch) * plane + (size_t)iy * Win + ix];
       }
 #pragma unroll
       for (int j = 0; j < kFillBatch; ++j) {
@@ -154,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __
 #pragma unroll
       for (int kx = 0; kx < KS; ++kx) {
         const int pp = ((wave * S + ky) * PW + (l32 * S + kx)) * PS + 8 * half;
-        const size_t wrow = ((size_t)(ky * KS + kx) * N + n0 + l32) * K + kc + 8 * half;
+        const size_t wrow = ((size_t)(ky * KS + kx) * Np + n0 + l32) * Kp + kc + 8 * half;
 #pragma unroll
         for (int kk = 0; kk < KC; kk += 16) {
           const uint4 bh = *reinterpret_cast<const uint4*>(&patch[0][pp + kk]);
@@ -162,7 +179,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __
           if constexpr (PREC == kPrecF16x3) bl = *reinterpret_cast<const uint4*>(&patch[NL - 1][pp + kk]);
 #pragma unroll
           for (int nb = 0; nb < 2; ++nb) {
-            const size_t wo = wrow + (size_t)nb * 32 * K + kk;
+            const size_t wo = wrow + (size_t)nb * 32 * Kp + kk;
             const uint4 ah = *reinterpret_cast<const uint4*>(wh + wo);
             uint4 al = ah;
             if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wl + wo);
@@ -181,6 +198,9 @@ __global__ __launch_bounds__(kThreads) void dd_conv_igemm_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int n = n0 + nb * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      if constexpr (RAGGED) {
+        if (n >= N) continue;
+      }
       if constexpr (SCATTER) {
         const int cout = N / 4, t4 = n / cout, co = n - t4 * cout;
         const size_t oy = 2 * (size_t)y + (t4 >> 1), ox = 2 * (size_t)x + (t4 & 1);
@@ -201,7 +221,8 @@ constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channe
 // P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
 //   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
 // part [splits][Cp][Cq][KS * KS]; grid ((Cp / 64) * (Cq / 64), splits).  A pixel tile is RH rows of 32 pixels.
-template <int PREC, int KS, int S, int PAD, int RH>
+// RAGGED: grid x is ceil(Cp / 64) * ceil(Cq / 64); channel rows >= Cp / Cq are filled as zeros and not stored (part keeps the real counts).
+template <int PREC, int KS, int S, int PAD, int RH, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __restrict__ P, const float* __restrict__ Q, float* __restrict__ part,
                                                                  int Cp, int Cq, int Hp, int Wp, int Hq, int Wq, int tiles_x, int tiles_y,
                                                                  long long tiles, int tiles_per_split) {
@@ -214,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
   __shared__ uint16_t QL[NL][64 * QCS] __attribute__((aligned(16)));
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
-  const int nq = Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int nq = RAGGED ? (Cq + 63) / 64 : Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
   const int wp = wave & 1, wq = wave >> 1;
   const size_t plane_p = (size_t)Hp * Wp, plane_q = (size_t)Hq * Wq;
 
@@ -237,7 +258,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
       for (int j = 0; j < kFillBatch; ++j) {
         const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, y = y0 + rem / 32, x = x0 + rem % 32;
         v[j] = 0.0f;
-        if (idx < 64 * PP && y < Hp && x < Wp) v[j] = P[((size_t)b * Cp + p0 + ch) * plane_p + (size_t)y * Wp + x];
+        if (idx < 64 * PP && (!RAGGED || p0 + ch < Cp) && y < Hp && x < Wp) v[j] = P[((size_t)b * Cp + p0 + ch) * plane_p + (size_t)y * Wp + x];
       }
 #pragma unroll
       for (int j = 0; j < kFillBatch; ++j) {
@@ -255,7 +276,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
       for (int j = 0; j < kFillBatch; ++j) {
         const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP, qr = rem / QW, y = qy0 + qr, x = qx0 + (rem - qr * QW);
         v[j] = 0.0f;
-        if (idx < 64 * QP && y >= 0 && y < Hq && x >= 0 && x < Wq) v[j] = Q[((size_t)b * Cq + q0 + ch) * plane_q + (size_t)y * Wq + x];
+        if (idx < 64 * QP && (!RAGGED || q0 + ch < Cq) && y >= 0 && y < Hq && x >= 0 && x < Wq) v[j] = Q[((size_t)b * Cq + q0 + ch) * plane_q + (size_t)y * Wq + x];
       }
 #pragma unroll
       for (int j = 0; j < kFillBatch; ++j) {
@@ -308,6 +329,9 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       const int p = p0 + wp * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      if constexpr (RAGGED) {
+        if (p >= Cp || q >= Cq) continue;
+      }
       dst[((size_t)p * Cq + q) * T + t] = acc[t][r];
     }
   }
@@ -321,19 +345,23 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
 // barrier in this kernel.  The weights are the A operand, 16 bytes per lane from the packed image (L1 / L2), as in the implicit GEMM.
 // grid (pixel tiles * N / (32 NB), B): the workgroups of one pixel tile are neighbours in dispatch order, so its re-reads for the other output
 // channels meet the cache.
-template <int PREC, int NB>
+// RAGGED (K, N multiples of 8): the weight image is the padded one of the pack kernel (rows of K rounded up to 32, N rounded up to 64 rows); the
+// pixel-side loads are guarded per 8-channel lane-half group -- K is a multiple of 8, so a tail is always a whole group -- and rows >= N are not
+// stored; N / (32 NB) rounds up.
+template <int PREC, int NB, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* __restrict__ in, const uint16_t* __restrict__ wh,
                                                                    const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N, int P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
-  const int nblocks = N / (32 * NB);
+  const int Kp = RAGGED ? padded(K, 32) : K;      // the weight image's row length
+  const int nblocks = RAGGED ? (N + 32 * NB - 1) / (32 * NB) : N / (32 * NB);
   const int n0 = (int)(blockIdx.x % (unsigned)nblocks) * (32 * NB), b = blockIdx.y;
   const int pw = (int)(blockIdx.x / (unsigned)nblocks) * kPwTile + wave * 32;      // first pixel of this wave
   if (pw >= P) return;                                                             // (the whole wave: nothing here waits for it)
   const int p = pw + l32;
   const bool live = p < P;
   const float* src = in + ((size_t)b * K + 8 * half) * (size_t)P + (live ? p : 0);
-  const uint16_t* wrow = wh + (size_t)(n0 + l32) * K + 8 * half;
-  const uint16_t* wrow_lo = wl + (size_t)(n0 + l32) * K + 8 * half;
+  const uint16_t* wrow = wh + (size_t)(n0 + l32) * Kp + 8 * half;
+  const uint16_t* wrow_lo = wl + (size_t)(n0 + l32) * Kp + 8 * half;
 
   f32x16_t acc[NB];
 #pragma unroll
@@ -341,12 +369,14 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* 
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[nb][i] = 0.0f;
 
-  for (int kc = 0; kc < K; kc += 32) {      // (K is a multiple of 64) sixteen loads in flight, then two MFMA steps
+  for (int kc = 0; kc < K; kc += 32) {      // (!RAGGED: K is a multiple of 64) sixteen loads in flight, then two MFMA steps
     float v[2][8];
 #pragma unroll
-    for (int s = 0; s < 2; ++s)
+    for (int s = 0; s < 2; ++s) {
+      const bool take = live && (!RAGGED || kc + 16 * s + 8 * half < K);      // this lane's eight channels: all below K, or none
 #pragma unroll
-      for (int e = 0; e < 8; ++e) v[s][e] = live ? src[(size_t)(kc + 16 * s + e) * P] : 0.0f;
+      for (int e = 0; e < 8; ++e) v[s][e] = take ? src[(size_t)(kc + 16 * s + e) * P] : 0.0f;
+    }
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
       u16x8_t vh, vl;
@@ -360,7 +390,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* 
       const uint4 bh = __builtin_bit_cast(uint4, vh), bl = __builtin_bit_cast(uint4, vl);
 #pragma unroll
       for (int nb = 0; nb < NB; ++nb) {
-        const size_t wo = (size_t)nb * 32 * K + kc + 16 * s;
+        const size_t wo = (size_t)nb * 32 * Kp + kc + 16 * s;
         const uint4 ah = *reinterpret_cast<const uint4*>(wrow + wo);
         uint4 al = ah;
         if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wrow_lo + wo);
@@ -375,7 +405,13 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* 
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) dst[(size_t)(nb * 32 + 8 * (r / 4) + (r % 4)) * P] = acc[nb][r];
+    for (int r = 0; r < 16; ++r) {
+      const int row = nb * 32 + 8 * (r / 4) + (r % 4);
+      if constexpr (RAGGED) {
+        if (n0 + 4 * half + row >= N) continue;
+      }
+      dst[(size_t)row * P] = acc[nb][r];
+    }
 }
 
 // ---- 1x1: weight gradient -----------------------------------------------------------------------------------------------------------------------------
@@ -386,7 +422,8 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* 
 // 2 l + 1 of the channel's LDS row -- the MFMA's K runs over the slots, and both operands use the same pixel -> slot map, so the products pair up
 // the same pixels.  Dword stores of consecutive lanes to consecutive addresses, 16-byte operand reads from rows of kPwTile + 8 halfs (the four
 // 16-lane groups of a 16-byte read meet every bank once): no 2-byte scatter or gather anywhere.
-template <int PREC>
+// RAGGED: as in dd_conv_wgrad_kernel -- the grid rounds the channel blocks up, rows >= Cp / Cq are filled as zeros and not stored.
+template <int PREC, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv1x1_wgrad_kernel(const float* __restrict__ Pm, const float* __restrict__ Q, float* __restrict__ part,
                                                                     int Cp, int Cq, int P, int tiles_per_plane, long long tiles, int tiles_per_split) {
   constexpr int RS = kPwTile + 8;      // halfs per channel row
@@ -396,7 +433,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_wgrad_kernel(const float*
   __shared__ uint16_t QL[NL][64 * RS] __attribute__((aligned(16)));
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
-  const int nq = Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int nq = RAGGED ? (Cq + 63) / 64 : Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
   const int wp = wave & 1, wq = wave >> 1;
 
   f32x16_t acc;
@@ -416,8 +453,14 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_wgrad_kernel(const float*
       for (int j = 0; j < kFillChannels; ++j) {
         const int row = r0 + 4 * j;
         const float* g = row < 64 ? Pm + ((size_t)b * Cp + p0 + row) * (size_t)P : Q + ((size_t)b * Cq + q0 + row - 64) * (size_t)P;
-        v[j][0] = live0 ? g[px] : 0.0f;
-        v[j][1] = live1 ? g[px + 64] : 0.0f;
+        bool take0 = live0, take1 = live1;
+        if constexpr (RAGGED) {
+          const bool in_range = row < 64 ? p0 + row < Cp : q0 + row - 64 < Cq;
+          take0 = take0 && in_range;
+          take1 = take1 && in_range;
+        }
+        v[j][0] = take0 ? g[px] : 0.0f;
+        v[j][1] = take1 ? g[px + 64] : 0.0f;
       }
 #pragma unroll
       for (int j = 0; j < kFillChannels; ++j) {
@@ -451,7 +494,12 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_wgrad_kernel(const float*
   // accumulator entry r of lane l: column q = l % 32, row p = 8 * (r / 4) + 4 * (l / 32) + r % 4
   float* dst = part + (size_t)split * Cp * Cq + (size_t)(p0 + wp * 32 + 4 * half) * Cq + q0 + wq * 32 + l32;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) dst[(size_t)(8 * (r / 4) + (r % 4)) * Cq] = acc[r];
+  for (int r = 0; r < 16; ++r) {
+    if constexpr (RAGGED) {
+      if (p0 + wp * 32 + 4 * half + 8 * (r / 4) + (r % 4) >= Cp || q0 + wq * 32 + l32 >= Cq) continue;
+    }
+    dst[(size_t)(8 * (r / 4) + (r % 4)) * Cq] = acc[r];
+  }
 }
 
 // grad_w[i] = part[0][i] + part[1][i] + ... in that order
@@ -468,70 +516,86 @@ constexpr int kWgradRowsConv = 2, kWgradRowsDeconv = 1;      // RH of the two we
 
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-template <int PREC>
+// RAGGED launches the guarded instantiations: grids round the channel blocks up, the packed image is the padded one (packed_halfs below)
+template <int PREC, bool RAGGED>
 hipError_t launch_conv_prec(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
                             hipStream_t st) {
-  const int taps = op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1;
-  const size_t nw = (size_t)taps * Cin * Cout;
+  const size_t nw = packed_halfs(op, dir, Cin, Cout);      // (!RAGGED: taps * Cin * Cout)
   uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
   uint16_t* wl = wh + nw;      // (only the split mode reads or writes it)
   if (op == kOpConv1) {
     const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin, P = H * W;
     const unsigned ptiles = (unsigned)((P + kPwTile - 1) / kPwTile);
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, dir == 0 ? kPackPwFwd : kPackPwBwd, N, K,
-                       1);
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl,
+                       dir == 0 ? kPackPwFwd : kPackPwBwd, N, K, 1, 32);
     if (N % 128 == 0)      // four 32-channel blocks per wave where the channels allow: half the re-reads of the input
-      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 4>), dim3(ptiles * (unsigned)(N / 128), (unsigned)B), dim3(kThreads), 0, st, in,
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 4, RAGGED>), dim3(ptiles * (unsigned)(N / 128), (unsigned)B), dim3(kThreads), 0, st, in,
                          (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
     else
-      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 2>), dim3(ptiles * (unsigned)(N / 64), (unsigned)B), dim3(kThreads), 0, st, in,
-                         (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 2, RAGGED>), dim3(ptiles * (unsigned)((N + 63) / 64), (unsigned)B), dim3(kThreads), 0, st,
+                         in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
     return hipGetLastError();
   }
   const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
   const unsigned tiles = (unsigned)tiles_x * (unsigned)tiles_y;
   if (op == kOpConv3) {
     const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, dir == 0 ? kPackConvFwd : kPackConvBwd, N,
-                       K, 9);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 3, 1, 1, 32, false>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
-                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl,
+                       dir == 0 ? kPackConvFwd : kPackConvBwd, N, K, 9, 32);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 3, 1, 1, 32, false, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
+                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
   } else if (dir == 0) {
     const int K = Cin, N = 4 * Cout;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvFwd, N, K, 1);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 1, 1, 0, 32, true>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
-                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvFwd, N, K, 1, 32);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 1, 1, 0, 32, true, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
+                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
   } else {
     const int K = Cout, N = Cin;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvBwd, N, K, 4);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 2, 2, 0, 16, false>), dim3(tiles, (unsigned)(N / kTileN), (unsigned)B), dim3(kThreads), 0, st, in,
-                       (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, 2 * H, 2 * W, H, W, tiles_x);
+    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvBwd, N, K, 4, 16);
+    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 2, 2, 0, 16, false, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
+                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, 2 * H, 2 * W, H, W, tiles_x);
   }
   return hipGetLastError();
 }
 
-template <int PREC>
+template <int PREC, bool RAGGED>
 hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                              hipStream_t st) {
   const WgradSplit sp = wgrad_split(op, B, H, W);
   const int tiles_x = (W + 31) / 32;
   float* part = reinterpret_cast<float*>(workspace);
-  const dim3 grid((unsigned)((Cin / 64) * (Cout / 64)), (unsigned)sp.splits);
+  const dim3 grid((unsigned)(((Cin + 63) / 64) * ((Cout + 63) / 64)), (unsigned)sp.splits);
   if (op == kOpConv1) {
-    hipLaunchKernelGGL((dd_conv1x1_wgrad_kernel<PREC>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H * W,
+    hipLaunchKernelGGL((dd_conv1x1_wgrad_kernel<PREC, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H * W,
                        (H * W + kPwTile - 1) / kPwTile, (long long)sp.tiles, sp.tiles_per_split);
   } else if (op == kOpConv3) {
     const int tiles_y = (H + kWgradRowsConv - 1) / kWgradRowsConv;
-    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, kWgradRowsConv>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H, W, H, W,
-                       tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, kWgradRowsConv, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H, W,
+                       H, W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
   } else {
     const int tiles_y = (H + kWgradRowsDeconv - 1) / kWgradRowsDeconv;
-    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, kWgradRowsDeconv>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout, H, W, 2 * H,
-                       2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, kWgradRowsDeconv, RAGGED>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout, H,
+                       W, 2 * H, 2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
   }
   const size_t total = (size_t)Cin * Cout * (op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1);
   hipLaunchKernelGGL(dd_conv_wgrad_reduce_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits);
   return hipGetLastError();
+}
+
+template <bool RAGGED>
+hipError_t launch_conv_ragged(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
+                              int prec, hipStream_t st) {
+  if (prec == kPrecBf16) return launch_conv_prec<kPrecBf16, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  if (prec == kPrecF16) return launch_conv_prec<kPrecF16, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  return launch_conv_prec<kPrecF16x3, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+}
+
+template <bool RAGGED>
+hipError_t launch_wgrad_ragged(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                               int prec, hipStream_t st) {
+  if (prec == kPrecBf16) return launch_wgrad_prec<kPrecBf16, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  if (prec == kPrecF16) return launch_wgrad_prec<kPrecF16, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  return launch_wgrad_prec<kPrecF16x3, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
 }
 
 }  // namespace
@@ -549,27 +613,41 @@ WgradSplit wgrad_split(int op, int B, int H, int W) {
   return s;
 }
 
+bool block64(int Cin, int Cout) {
+  return Cin >= 64 && Cin <= 1536 && Cin % 64 == 0 && Cout >= 64 && Cout <= 1536 && Cout % 64 == 0;
+}
+
+// halfs of the packed image wp[tap][Np][Kp] of one direction: Np = N rounded up to kTileN, Kp = K rounded up to the K step of the GEMM kernel that
+// reads it (32; 16 for the transpose convolution's data gradient).  The GEMM kernels read ALL of it, 16 bytes at a time: this is the size the pack
+// kernel writes and the size workspace_bytes must cover.  For block-64 channel counts it is taps * Cin * Cout.
+size_t packed_halfs(int op, int dir, int Cin, int Cout) {
+  int taps, N, K, kstep = 32;
+  if (op == kOpDeconv2 && dir == 0) { taps = 1; N = 4 * Cout; K = Cin; }
+  else if (op == kOpDeconv2) { taps = 4; N = Cin; K = Cout; kstep = 16; }
+  else { taps = op == kOpConv3 ? 9 : 1; N = dir == 0 ? Cout : Cin; K = dir == 0 ? Cin : Cout; }
+  return (size_t)taps * (size_t)padded(N, kTileN) * (size_t)padded(K, kstep);
+}
+
 size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec) {
   const size_t taps = op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1;
-  const size_t nw = taps * (size_t)Cin * (size_t)Cout;
-  const size_t packed = nw * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
-  const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * nw * sizeof(float);
+  const size_t fwd = packed_halfs(op, 0, Cin, Cout), bwd = packed_halfs(op, 1, Cin, Cout);
+  const size_t packed = (fwd > bwd ? fwd : bwd) * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);      // hi, and lo behind it in the split mode
+  const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * taps * (size_t)Cin * (size_t)Cout * sizeof(float);
   const size_t need = packed > partials ? packed : partials;
   return (need + 255) / 256 * 256;
 }
 
+// a shape of the block-64 contract runs the block-64 instantiations, whichever entry point it came through; only the others run the guarded ones
 hipError_t launch_conv(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
                        int prec, hipStream_t st) {
-  if (prec == kPrecBf16) return launch_conv_prec<kPrecBf16>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
-  if (prec == kPrecF16) return launch_conv_prec<kPrecF16>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
-  return launch_conv_prec<kPrecF16x3>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  if (block64(Cin, Cout)) return launch_conv_ragged<false>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, prec, st);
+  return launch_conv_ragged<true>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, prec, st);
 }
 
 hipError_t launch_wgrad(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                         int prec, hipStream_t st) {
-  if (prec == kPrecBf16) return launch_wgrad_prec<kPrecBf16>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
-  if (prec == kPrecF16) return launch_wgrad_prec<kPrecF16>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
-  return launch_wgrad_prec<kPrecF16x3>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  if (block64(Cin, Cout)) return launch_wgrad_ragged<false>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, prec, st);
+  return launch_wgrad_ragged<true>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, prec, st);
 }
 
 }  // namespace ddconv

@@ -81,7 +81,11 @@ class DDIMDepthEstimate_Res(nn.Module):
                            other precision and the MPViT widths keep the torch convolutions; same state-dict keys; eval unchanged).
                            "hip+neck" does the same and, on the HAHI heads, also converts the neck's convolutions (eight 1x1, four 3x3) with
                            ``convert_hip_conv(self.hahineck, precision, pointwise=True)``; Swin-L's ``trans_fusion.2`` (2048 input channels,
-                           beyond the library's 1536) stays nn.Conv2d.  On a head without a neck "hip+neck" equals "hip".
+                           beyond the block-64 contract's 1536) stays nn.Conv2d.  On a head without a neck "hip+neck" equals "hip".
+                           "hip+all" is "hip+neck" on the extended channel contract (``channels="any"``: multiples of 8 in 8..2048 through
+                           dd_convx_*): every FPN and neck convolution of every registered head is converted, the MPViT widths (216 / 288)
+                           and Swin-L's 2048 -> 1536 ``trans_fusion.2`` included.  A site the block-64 contract takes runs the same kernels
+                           and gives the same bits as with "hip" / "hip+neck"; on a Res head "hip+all" builds what "hip" builds.
         codec_backend      "torch" [default] or "hip" (None = $DDEPTH_CODEC_BACKEND, else "torch"): with "hip" the four convolutions of
                            ``depth_transform`` become codec.HipCodecConv2d / codec.HipCodecConvTranspose2d holding the same tensors and the
                            decoder's nn.Sigmoid a codec.HipCodecTail, so their .train() forward and backward run in csrc/dd_codec.hip in
@@ -156,18 +160,20 @@ class DDIMDepthEstimate_Res(nn.Module):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
         self.conv_backend = resolve_conv_backend(conv_backend)
-        if self.conv_backend in ("hip", "hip+neck"):
+        channels = "any" if self.conv_backend == "hip+all" else "block64"
+        if self.conv_backend in ("hip", "hip+neck", "hip+all"):
             # (convup_fp never runs; it is converted too, for uniformity)
             for name in ("conv_lateral", "conv_up", "convup_fp"):
                 if hasattr(self, name):
-                    setattr(self, name, convert_hip_conv(getattr(self, name), precision))
+                    setattr(self, name, convert_hip_conv(getattr(self, name), precision, False, channels))
         self.codec_backend = resolve_codec_backend(codec_backend)
         if self.codec_backend == "hip":
             convert_hip_codec(self.depth_transform)
-        if self.conv_backend == "hip+neck" and self._HAHI:
-            # the neck's 1x1 (lateral_convs, conv_proj, trans_proj) and 3x3 (conv_fusion, trans_fusion) convolutions; what the library does not
-            # support -- Swin-L's trans_fusion.2 with 2048 input channels, most MPViT widths -- stays nn.Conv2d
-            self.hahineck = convert_hip_conv(self.hahineck, precision, pointwise=True)
+        if self.conv_backend in ("hip+neck", "hip+all") and self._HAHI:
+            # the neck's 1x1 (lateral_convs, conv_proj, trans_proj) and 3x3 (conv_fusion, trans_fusion) convolutions; with "hip+neck", what the
+            # block-64 contract does not take -- Swin-L's trans_fusion.2 with 2048 input channels, most MPViT widths -- stays nn.Conv2d; with
+            # "hip+all" all twelve are converted
+            self.hahineck = convert_hip_conv(self.hahineck, precision, True, channels)
 
     @staticmethod
     def _on_hip(tensors) -> bool:

@@ -15,7 +15,12 @@
  * precision: a dd_precision value (ddepth.h).  DD_PREC_BF16 / DD_PREC_F16 round both operands to 16 bits once and contract them on
  * v_mfma_f32_32x32x16_{bf16,f16}; DD_PREC_F16X3 carries every operand as the f16 pair hi = f16(v), lo = f16(v - hi) and contracts
  * hi.hi + hi.lo + lo.hi (three MFMAs per product).  Every other value returns DD_ERR_UNSUPPORTED.
- * Channels: Cin and Cout multiples of 64 in 64 .. 1536; anything else returns DD_ERR_UNSUPPORTED.  H, W >= 1 are arbitrary.
+ * Channels: two contracts.  dd_conv_supported, dd_conv_workspace_bytes and the nine dd_conv3x3_* / dd_deconv2x2_* / dd_conv1x1_* functions take
+ * Cin and Cout that are multiples of 64 in 64 .. 1536 (the block-64 contract).  The five dd_convx_* functions take the extended range, a
+ * superset: Cin and Cout multiples of 8 in 8 .. 2048 (every width of every registered head).  Through them a block-64 shape runs the same
+ * kernels and gives the same bits as through the nine; any other shape runs guarded kernels that treat the channels beyond the count as zeros,
+ * with the same accumulation order, so the result equals that of the tensors zero-padded to the next multiple of 64.  Channel counts outside
+ * the contract of the function called return DD_ERR_UNSUPPORTED.  H, W >= 1 are arbitrary.
  *
  * Results are bitwise reproducible: no floating-point atomics; the weight gradient's partial sums over the pixel dimension are combined
  * in a fixed order by a second launch.
@@ -69,6 +74,23 @@ int dd_conv1x1_backward_data(const float* grad_y, const float* w, float* grad_x,
                              int precision, void* stream);
 int dd_conv1x1_backward_weight(const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                                int precision, void* stream);
+
+/* ---- the extended channel range: Cin, Cout multiples of 8 in 8 .. 2048; `op` is a dd_conv_op, tensors and H, W as for that operator above ---- */
+
+/* 1 where (op, Cin, Cout, precision) runs through dd_convx_*, else 0.  No side effects. */
+int dd_convx_supported(int op, int Cin, int Cout, int precision);
+
+/* As dd_conv_workspace_bytes.  The packed weights are padded to whole tiles (Cout, or Cin in the data gradient, to a multiple of 64; the
+ * other count to a multiple of 32) and the size covers that; a workspace of the size dd_conv_workspace_bytes would give for rounded-down
+ * counts is too small.  The weight gradient's partials grow with the range: 3x3, 2048 -> 1536, B = 4, 11 x 38 needs about 680 MB. */
+int dd_convx_workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int precision, int64_t* bytes);
+
+int dd_convx_forward(int op, const float* x, const float* w, float* y, void* workspace, int B, int Cin, int Cout, int H, int W, int precision,
+                     void* stream);
+int dd_convx_backward_data(int op, const float* grad_y, const float* w, float* grad_x, void* workspace, int B, int Cin, int Cout, int H, int W,
+                           int precision, void* stream);
+int dd_convx_backward_weight(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
+                             int precision, void* stream);
 
 #ifdef __cplusplus
 }

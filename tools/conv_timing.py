@@ -8,6 +8,7 @@
     (d) the same, precision f16x3
 
     python tools/conv_timing.py [--out profiles/conv_timing.json] [--windows 7] [--heads res,swin] [--sites lateral0,up1]
+    python tools/conv_timing.py --channels any --heads mpvit      # the MPViT-small laterals through the extended channel range (dd_convx_*)
 
 Method: every variant of a site is warmed up; a timed window is CALLS forward + backward passes (input and weight gradient) between two device
 events; inside one repeat the variants are timed one after another (so drift hits all alike), and the median over the repeats is reported with
@@ -42,7 +43,8 @@ from diffusiondepth_amd import conv as CV  # noqa: E402
 HBM_PEAK = 8.0e12          # B/s, MI355X spec
 MFMA_PEAK = 2.5168e15      # flop/s, bf16 / f16 dense MFMA, MI355X spec (16 x the 157.3 TF fp32 matrix rate)
 B, H, W = 4, 352, 1216     # KITTI crop
-HEADS = {"res": ((64, 128, 256, 512), 2), "swin": ((192, 384, 768, 1536), 4)}      # pyramid widths, stride of the first level
+# pyramid widths, stride of the first level.  "mpvit" (MPViT-small: 216 and 288 are no multiples of 64) needs --channels any
+HEADS = {"res": ((64, 128, 256, 512), 2), "swin": ((192, 384, 768, 1536), 4), "mpvit": ((128, 216, 288, 288), 4)}
 STEP_COMMANDS = ["python bench.py --mode train-dp --variant res --batch 4",
                  "DDEPTH_CONV_BACKEND=hip python bench.py --mode train-dp --variant res --batch 4",
                  "DDEPTH_CONV_BACKEND=hip DDEPTH_BN_BACKEND=hip python bench.py --mode train-dp --variant res --batch 4"]
@@ -78,7 +80,9 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--heads", default="res,swin")
     ap.add_argument("--sites", default="")
+    ap.add_argument("--channels", default="block64", choices=CV.CHANNELS, help="the channel contract of the HipConv* modules (conv.CHANNELS)")
     args = ap.parse_args()
+    extra = (args.channels,) if args.channels != "block64" else ()
     if not torch.cuda.is_available():
         sys.exit("conv_timing: no GPU visible to PyTorch -- this tool measures, it has no CPU path")
     if args.windows < 5:
@@ -99,7 +103,11 @@ def main():
             def make(prec):
                 if prec is None:
                     return (nn.Conv2d(cin, cout, 3, 1, 1, bias=False) if op == CV.OP_CONV3X3 else nn.ConvTranspose2d(cin, cout, 2, 2, bias=False)).cuda()
-                return (CV.HipConv2d(cin, cout, precision=prec) if op == CV.OP_CONV3X3 else CV.HipConvTranspose2d(cin, cout, precision=prec)).cuda()
+                m = (CV.HipConv2d(cin, cout, precision=prec) if op == CV.OP_CONV3X3 else CV.HipConvTranspose2d(cin, cout, precision=prec)).cuda()
+                m.channels = args.channels
+                if not CV.supported(op, cin, cout, prec, args.channels):
+                    sys.exit(f"conv_timing: {name} {cin} -> {cout} is not supported with --channels {args.channels}: it would time torch's convolution")
+                return m
 
             mods = {"a_fp32": make(None), "b_autocast_bf16": make(None), "c_hip_bf16": make("bf16"), "d_hip_f16x3": make("f16x3")}
 
@@ -125,8 +133,9 @@ def main():
                     times[key].append(window(lambda: step(key), calls))
             # the three library calls of (c), one call per window
             xd, wd, pid = x.detach(), mods["c_hip_bf16"].weight.detach(), CV.precision_id("bf16")
-            kern = {"forward": lambda: CV.conv_forward(op, xd, wd, pid), "backward_data": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid),
-                    "backward_weight": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid)}
+            kern = {"forward": lambda: CV.conv_forward(op, xd, wd, pid, *extra),
+                    "backward_data": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid, *extra),
+                    "backward_weight": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid, *extra)}
             nbytes = {"forward": 4 * (xd.numel() + wd.numel() + gy.numel()), "backward_data": 4 * (xd.numel() + wd.numel() + gy.numel()),
                       "backward_weight": 4 * (xd.numel() + wd.numel() + gy.numel())}
             ktimes = {k: [] for k in kern}
@@ -163,7 +172,7 @@ def main():
     for c in STEP_COMMANDS:
         print("    " + c)
     result = {"tool": "conv_timing", "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "mfma_peak_flops_per_s": MFMA_PEAK,
-              "sites": rows, "sum_ms": total, "step_commands": STEP_COMMANDS}
+              "channels": args.channels, "sites": rows, "sum_ms": total, "step_commands": STEP_COMMANDS}
     line = json.dumps(result)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -12,6 +12,9 @@ and one more row: the whole neck (necks.HAHIHeteroNeck, .train(), forward + back
 convert_hip_conv(neck, "bf16", pointwise=True).
 
     python tools/neck_conv_timing.py [--out profiles/neck_conv_timing.json] [--windows 7] [--sites lateral0,conv_proj] [--no-neck]
+    python tools/neck_conv_timing.py --channels any      # the extended channel range (dd_convx_*): Swin-L trans_fusion.2 (2048 -> 1536) and the twelve
+                                                         # neck sites of MPViT-small (128 / 216 / 288 / 288), plus the block-64 Swin-L sites again through
+                                                         # channels="any" (same kernels: they should agree with the default run within its spread)
 
 Method: every variant of a site is warmed up; a timed window is CALLS forward + backward passes (input and weight gradient) between two device
 events; inside one repeat the variants are timed one after another (so drift hits all alike), and the median over the repeats is reported with
@@ -60,6 +63,20 @@ def sites():
     return out
 
 
+def sites_any():
+    """--channels any: what only the extended range takes -- Swin-L trans_fusion.2 and the MPViT-small neck (names prefixed) -- then the block-64
+    Swin-L sites once more, which run the same kernels through the other entry points."""
+    lv = levels()
+    out = [("swin_trans_fusion2", 3, CHANS[3] + EMBED, CHANS[3], *lv[3])]
+    mp = (128, 216, 288, 288)
+    out += [(f"mpvit_lateral{i}", 1, c, c, *lv[i]) for i, c in enumerate(mp)]
+    out.append(("mpvit_conv_proj", 1, mp[0], EMBED, *lv[0]))
+    out += [(f"mpvit_trans_proj{j}", 1, mp[j + 1], EMBED, *lv[j + 1]) for j in range(3)]
+    out.append(("mpvit_conv_fusion", 3, mp[0] + EMBED, mp[0], *lv[0]))
+    out += [(f"mpvit_trans_fusion{j}", 3, mp[j + 1] + EMBED, mp[j + 1], *lv[j + 1]) for j in range(3)]
+    return out + sites()
+
+
 def window(fn, calls):
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
@@ -79,8 +96,11 @@ def not_slower(c, a):
     return bool(c["median_ms"] <= a["median_ms"] + max(a["max_ms"] - a["min_ms"], c["max_ms"] - c["min_ms"]))
 
 
-def time_site(name, k, cin, cout, h, w, windows):
+def time_site(name, k, cin, cout, h, w, windows, channels="block64"):
     op = CV.OP_CONV3X3 if k == 3 else CV.OP_CONV1X1
+    extra = (channels,) if channels != "block64" else ()
+    if not CV.supported(op, cin, cout, "bf16", channels):
+        sys.exit(f"neck_conv_timing: {name} {cin} -> {cout} is not supported with --channels {channels}: it would time torch's convolution")
     x = torch.randn(B, cin, h, w, device="cuda").requires_grad_(True)
     gy = torch.randn(B, cout, h, w, device="cuda")
     gy16 = gy.bfloat16()
@@ -88,7 +108,9 @@ def time_site(name, k, cin, cout, h, w, windows):
     def make(prec):
         if prec is None:
             return nn.Conv2d(cin, cout, k, 1, k // 2, bias=False).cuda()
-        return CV.HipConv2d(cin, cout, k, 1, k // 2, precision=prec).cuda()
+        m = CV.HipConv2d(cin, cout, k, 1, k // 2, precision=prec).cuda()
+        m.channels = channels
+        return m
 
     mods = {"a_fp32": make(None), "b_autocast_bf16": make(None), "c_hip_bf16": make("bf16"), "d_hip_f16x3": make("f16x3")}
 
@@ -114,8 +136,8 @@ def time_site(name, k, cin, cout, h, w, windows):
             times[key].append(window(lambda: step(key), calls))
     # the three library calls of (c), one call per window
     xd, wd, pid = x.detach(), mods["c_hip_bf16"].weight.detach(), CV.precision_id("bf16")
-    kern = {"forward": lambda: CV.conv_forward(op, xd, wd, pid), "backward_data": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid),
-            "backward_weight": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid)}
+    kern = {"forward": lambda: CV.conv_forward(op, xd, wd, pid, *extra), "backward_data": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid, *extra),
+            "backward_weight": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid, *extra)}
     nbytes = 4 * (xd.numel() + wd.numel() + gy.numel())
     ktimes = {kk: [] for kk in kern}
     for fn in kern.values():
@@ -183,6 +205,7 @@ def main():
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--sites", default="")
     ap.add_argument("--no-neck", action="store_true")
+    ap.add_argument("--channels", default="block64", choices=CV.CHANNELS, help="the channel contract of the HipConv2d modules; 'any' times sites_any()")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("neck_conv_timing: no GPU visible to PyTorch -- this tool measures, it has no CPU path")
@@ -191,15 +214,15 @@ def main():
     torch.cuda.set_device(0)
     want = set(filter(None, args.sites.split(",")))
     rows = []
-    for site in sites():
+    for site in (sites_any() if args.channels == "any" else sites()):
         if want and site[0] not in want:
             continue
-        rows.append(time_site(*site, args.windows))
+        rows.append(time_site(*site, args.windows, args.channels))
         torch.cuda.empty_cache()
     total = {k: sum(r["fwd_bwd"][k]["median_ms"] for r in rows) for k in VARIANTS}
     print("sum over the sites, ms: " + "  ".join(f"{k} {v:.3f}" for k, v in total.items()))
-    neck = None if args.no_neck else time_neck(args.windows)
-    result = {"tool": "neck_conv_timing", "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "mfma_peak_flops_per_s": MFMA_PEAK,
+    neck = None if (args.no_neck or args.channels == "any") else time_neck(args.windows)
+    result = {"tool": "neck_conv_timing", "channels": args.channels, "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "mfma_peak_flops_per_s": MFMA_PEAK,
               "sites": rows, "sum_ms": total, "whole_neck": neck}
     line = json.dumps(result)
     if args.out:
