@@ -2,43 +2,25 @@
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_bn.h"
 #include "dd_bn.h"
+#include "dd_status.h"
 
 #include <climits>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <string>
 
 namespace {
 
-thread_local std::string g_bn_err;
-
-int bn_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_bn_err = buf;
-  return code;
-}
-
-#define BN_HIP(expr)                                                                            \
-  do {                                                                                          \
-    hipError_t _e = (expr);                                                                     \
-    if (_e != hipSuccess) return bn_fail(DD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
+thread_local ddstatus::LastError g_bn_err;
 
 int check_shape(int B, int C, int HW) {
-  if (B < 1 || C < 1 || HW < 1) return bn_fail(DD_ERR_INVALID_ARG, "B, C, HW must be positive (got %d, %d, %d)", B, C, HW);
-  if (B > 65535 || C > 65535) return bn_fail(DD_ERR_INVALID_ARG, "B = %d, C = %d: at most 65535 each per call", B, C);
+  if (B < 1 || C < 1 || HW < 1) return g_bn_err.fail(DD_ERR_INVALID_ARG, "B, C, HW must be positive (got %d, %d, %d)", B, C, HW);
+  if (B > 65535 || C > 65535) return g_bn_err.fail(DD_ERR_INVALID_ARG, "B = %d, C = %d: at most 65535 each per call", B, C);
   return DD_OK;
 }
 
 int check_act(int act, float slope) {
   if (act != DD_BN_ACT_NONE && act != DD_BN_ACT_RELU && act != DD_BN_ACT_LEAKY_RELU)
-    return bn_fail(DD_ERR_INVALID_ARG, "act must be a dd_bn_act value (got %d)", act);
-  if (act == DD_BN_ACT_LEAKY_RELU && !std::isfinite(slope)) return bn_fail(DD_ERR_INVALID_ARG, "slope must be finite");
+    return g_bn_err.fail(DD_ERR_INVALID_ARG, "act must be a dd_bn_act value (got %d)", act);
+  if (act == DD_BN_ACT_LEAKY_RELU && !std::isfinite(slope)) return g_bn_err.fail(DD_ERR_INVALID_ARG, "slope must be finite");
   return DD_OK;
 }
 
@@ -46,59 +28,59 @@ int check_act(int act, float slope) {
 
 extern "C" {
 
-const char* dd_bn_last_error(void) { return g_bn_err.c_str(); }
+const char* dd_bn_last_error(void) { return g_bn_err.text.c_str(); }
 
 int dd_bn_workspace_bytes(int B, int C, int HW, int64_t* bytes) {
-  if (!bytes) return bn_fail(DD_ERR_INVALID_ARG, "bytes is NULL");
+  if (!bytes) return g_bn_err.fail(DD_ERR_INVALID_ARG, "bytes is NULL");
   if (int rc = check_shape(B, C, HW)) return rc;
   *bytes = (int64_t)ddbn::workspace_bytes(B, C, HW);
   return DD_OK;
 }
 
 int dd_bn_stats(const float* x, double* sums, void* workspace, int B, int C, int HW, void* stream) {
-  if (!x || !sums || !workspace) return bn_fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (!x || !sums || !workspace) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
   if (int rc = check_shape(B, C, HW)) return rc;
-  BN_HIP(ddbn::launch_stats(x, sums, workspace, B, C, HW, (hipStream_t)stream));
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_stats(x, sums, workspace, B, C, HW, (hipStream_t)stream));
   return DD_OK;
 }
 
 int dd_bn_finalize(const double* sums, float eps, float momentum, float* mean_invstd, float* running_mean, float* running_var, int C,
                    void* stream) {
-  if (!sums || !mean_invstd) return bn_fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (!sums || !mean_invstd) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
   if ((running_mean == nullptr) != (running_var == nullptr))
-    return bn_fail(DD_ERR_INVALID_ARG, "running_mean and running_var: both or neither");
-  if (C < 1 || C > 65535) return bn_fail(DD_ERR_INVALID_ARG, "C must be in 1..65535 (got %d)", C);
-  if (!(eps >= 0.0f)) return bn_fail(DD_ERR_INVALID_ARG, "eps must be >= 0 (got %g)", (double)eps);
-  BN_HIP(ddbn::launch_finalize(sums, eps, momentum, mean_invstd, running_mean, running_var, C, (hipStream_t)stream));
+    return g_bn_err.fail(DD_ERR_INVALID_ARG, "running_mean and running_var: both or neither");
+  if (C < 1 || C > 65535) return g_bn_err.fail(DD_ERR_INVALID_ARG, "C must be in 1..65535 (got %d)", C);
+  if (!(eps >= 0.0f)) return g_bn_err.fail(DD_ERR_INVALID_ARG, "eps must be >= 0 (got %g)", (double)eps);
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_finalize(sums, eps, momentum, mean_invstd, running_mean, running_var, C, (hipStream_t)stream));
   return DD_OK;
 }
 
 int dd_bn_apply(const float* x, const float* mean_invstd, const float* weight, const float* bias, float* y, int act, float slope, int B,
                 int C, int HW, void* stream) {
-  if (!x || !mean_invstd || !y) return bn_fail(DD_ERR_INVALID_ARG, "null pointer");
-  if (x == y) return bn_fail(DD_ERR_INVALID_ARG, "y may not alias x (the backward reads x)");
+  if (!x || !mean_invstd || !y) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (x == y) return g_bn_err.fail(DD_ERR_INVALID_ARG, "y may not alias x (the backward reads x)");
   if (int rc = check_shape(B, C, HW)) return rc;
   if (int rc = check_act(act, slope)) return rc;
-  BN_HIP(ddbn::launch_apply(x, mean_invstd, weight, bias, y, act, slope, B, C, HW, (hipStream_t)stream));
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_apply(x, mean_invstd, weight, bias, y, act, slope, B, C, HW, (hipStream_t)stream));
   return DD_OK;
 }
 
 int dd_bn_backward_reduce(const float* x, const float* grad_y, const float* mean_invstd, const float* weight, const float* bias, int act,
                           float slope, double* sums2, void* workspace, int B, int C, int HW, void* stream) {
-  if (!x || !grad_y || !mean_invstd || !sums2 || !workspace) return bn_fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (!x || !grad_y || !mean_invstd || !sums2 || !workspace) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
   if (int rc = check_shape(B, C, HW)) return rc;
   if (int rc = check_act(act, slope)) return rc;
-  BN_HIP(ddbn::launch_backward_reduce(x, grad_y, mean_invstd, weight, bias, act, slope, sums2, workspace, B, C, HW, (hipStream_t)stream));
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_backward_reduce(x, grad_y, mean_invstd, weight, bias, act, slope, sums2, workspace, B, C, HW, (hipStream_t)stream));
   return DD_OK;
 }
 
 int dd_bn_backward_apply(const float* x, const float* grad_y, const float* mean_invstd, const float* weight, const float* bias,
                          const double* sums2, const double* sums, float* grad_x, int act, float slope, int B, int C, int HW, void* stream) {
-  if (!x || !grad_y || !mean_invstd || !sums2 || !sums || !grad_x) return bn_fail(DD_ERR_INVALID_ARG, "null pointer");
-  if (grad_x == x || grad_x == grad_y) return bn_fail(DD_ERR_INVALID_ARG, "grad_x may not alias x or grad_y");
+  if (!x || !grad_y || !mean_invstd || !sums2 || !sums || !grad_x) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (grad_x == x || grad_x == grad_y) return g_bn_err.fail(DD_ERR_INVALID_ARG, "grad_x may not alias x or grad_y");
   if (int rc = check_shape(B, C, HW)) return rc;
   if (int rc = check_act(act, slope)) return rc;
-  BN_HIP(ddbn::launch_backward_apply(x, grad_y, mean_invstd, weight, bias, sums2, sums, grad_x, act, slope, B, C, HW, (hipStream_t)stream));
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_backward_apply(x, grad_y, mean_invstd, weight, bias, sums2, sums, grad_x, act, slope, B, C, HW, (hipStream_t)stream));
   return DD_OK;
 }
 

@@ -15,6 +15,7 @@ constexpr int kThreads = 256;            // 4 waves of 64
 constexpr int kTileH = 4, kTileW = 32;   // output pixels of one workgroup of the implicit GEMM: one 32-pixel row per wave
 constexpr int kTileN = 64;               // output channels of one workgroup
 constexpr int kPwTile = 128;             // 1x1: consecutive pixels of ONE plane a workgroup owns (32 per wave), forward, data and weight gradient alike
+constexpr int kPwKStep = 32;             // 1x1: channels per turn of the GEMM kernel's K loop (two MFMA steps), what its weight rows are padded to
 constexpr int kSplitTiles = 8;           // pixel tiles one workgroup of the weight gradient adds up, at least
 constexpr int kMaxSplits = 64;           // pixel splits of the weight gradient at most (the tiles per split grow beyond)
 
@@ -26,10 +27,15 @@ struct WgradSplit {
 };
 WgradSplit wgrad_split(int op, int B, int H, int W);
 
-// Channel counts.  The block-64 contract (multiples of 64 in 64..1536) runs the unguarded instantiations; every other pair of multiples of 8 in
-// 8..2048 (the extended contract of dd_convx_*, checked in dd_api_conv.cpp) runs the guarded ("ragged") ones, which fill channels beyond the
-// count as zeros, store only real rows, and read a weight image padded to whole tiles.  launch_conv / launch_wgrad choose by the shape alone.
-bool block64(int Cin, int Cout);
+// Channel counts: the two contracts of include/ddepth_conv.h, said here once for the argument checks of dd_api_conv.cpp and for the launchers.
+// A pair inside the block-64 contract runs the unguarded instantiations; every other pair of the extended contract (dd_convx_*) runs the guarded
+// ("ragged") ones, which fill channels beyond the count as zeros, store only real rows, and read a weight image padded to whole tiles.
+// launch_conv / launch_wgrad choose by the shape alone.
+enum ChannelContract { kChannelsBlock64, kChannelsExtended };
+constexpr bool channels_block64(int c) { return c >= 64 && c <= 1536 && c % 64 == 0; }
+constexpr bool channels_extended(int c) { return c >= 8 && c <= 2048 && c % 8 == 0; }
+constexpr bool channels_ok(ChannelContract contract, int c) { return contract == kChannelsBlock64 ? channels_block64(c) : channels_extended(c); }
+bool block64(int Cin, int Cout);      // both counts inside the block-64 contract
 
 // halfs of the packed weight image of one direction (dir as in launch_conv): taps * (N rounded up to kTileN) * (K rounded up to the GEMM's K
 // step); taps * Cin * Cout for block-64 counts

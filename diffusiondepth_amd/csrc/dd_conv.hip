@@ -20,9 +20,14 @@
 //   dd_conv1x1_gemm_kernel  the 1x1 forward / data gradient: no halo, so a workgroup owns 128 consecutive pixels of a flat plane and the pixel-side MFMA
 //   dd_conv1x1_wgrad_kernel operand comes straight from coalesced dword loads (no LDS); the 1x1 weight gradient contracts over the pixels, contiguous for
 //                           both operands, through dword LDS stores and 16-byte reads (comments at the kernels).
+//   host side               gemm_kind(op, dir) is the one table of <KS, S, PAD, KC, SCATTER> and pack mode, gemm_shape adds N and K; the pack launch,
+//                           the GEMM launch, packed_halfs and workspace_bytes read them, so the three that must agree on the padded weight image to
+//                           the byte cannot drift apart.  dispatch() turns the runtime operand mode and channel contract into template arguments.
 //
 // Plain HIP C++ and compiler builtins; every write to memory is a plain C++ store.  Only constructs the host emulation of the tests provides.
 #include "dd_conv.h"
+
+#include <type_traits>
 
 namespace ddconv {
 
@@ -345,14 +350,14 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_kernel(const float* __
 // barrier in this kernel.  The weights are the A operand, 16 bytes per lane from the packed image (L1 / L2), as in the implicit GEMM.
 // grid (pixel tiles * N / (32 NB), B): the workgroups of one pixel tile are neighbours in dispatch order, so its re-reads for the other output
 // channels meet the cache.
-// RAGGED (K, N multiples of 8): the weight image is the padded one of the pack kernel (rows of K rounded up to 32, N rounded up to 64 rows); the
+// RAGGED (K, N multiples of 8): the weight image is the padded one of the pack kernel (rows of K rounded up to kPwKStep, N rounded up to 64 rows); the
 // pixel-side loads are guarded per 8-channel lane-half group -- K is a multiple of 8, so a tail is always a whole group -- and rows >= N are not
 // stored; N / (32 NB) rounds up.
 template <int PREC, int NB, bool RAGGED>
 __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* __restrict__ in, const uint16_t* __restrict__ wh,
                                                                    const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N, int P) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
-  const int Kp = RAGGED ? padded(K, 32) : K;      // the weight image's row length
+  const int Kp = RAGGED ? padded(K, kPwKStep) : K;      // the weight image's row length
   const int nblocks = RAGGED ? (N + 32 * NB - 1) / (32 * NB) : N / (32 * NB);
   const int n0 = (int)(blockIdx.x % (unsigned)nblocks) * (32 * NB), b = blockIdx.y;
   const int pw = (int)(blockIdx.x / (unsigned)nblocks) * kPwTile + wave * 32;      // first pixel of this wave
@@ -369,7 +374,7 @@ __global__ __launch_bounds__(kThreads) void dd_conv1x1_gemm_kernel(const float* 
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[nb][i] = 0.0f;
 
-  for (int kc = 0; kc < K; kc += 32) {      // (!RAGGED: K is a multiple of 64) sixteen loads in flight, then two MFMA steps
+  for (int kc = 0; kc < K; kc += kPwKStep) {      // (!RAGGED: K is a multiple of 64) sixteen loads in flight, then two MFMA steps
     float v[2][8];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -512,48 +517,77 @@ __global__ __launch_bounds__(kThreads) void dd_conv_wgrad_reduce_kernel(const fl
   grad_w[i] = s;
 }
 
-constexpr int kWgradRowsConv = 2, kWgradRowsDeconv = 1;      // RH of the two weight-gradient instantiations (LDS: 58.5 KB / 43.5 KB split-f16)
-
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-// RAGGED launches the guarded instantiations: grids round the channel blocks up, the packed image is the padded one (packed_halfs below)
+// ---- one description of each GEMM ---------------------------------------------------------------------------------------------------------------------
+// The forward (dir 0) / data gradient (dir 1) of an operator as the GEMM D[n][pixel] += wp[tap][n][k] . patch[pixel + tap][k]: the arguments its kernel
+// template is instantiated with, the K step its weight image is padded to, and the pack mode.  The ONLY place that says them: gemm_shape adds the
+// channel counts, and the pack launch, the GEMM launch, packed_halfs and workspace_bytes read these two.
+struct GemmKind {
+  int ks, stride, pad, kstep, pack_mode;
+  bool scatter;
+};
+constexpr GemmKind gemm_kind(int op, int dir) {
+  if (op == kOpConv3) return {3, 1, 1, 32, dir == 0 ? kPackConvFwd : kPackConvBwd, false};
+  if (op == kOpConv1) return {1, 1, 0, kPwKStep, dir == 0 ? kPackPwFwd : kPackPwBwd, false};
+  if (dir == 0) return {1, 1, 0, 32, kPackDeconvFwd, true};      // N = 4 Cout: GEMM column (dy * 2 + dx) * Cout + co, scattered by the epilogue
+  return {2, 2, 0, 16, kPackDeconvBwd, false};                   // ... and gathered again: four taps of stride 2
+}
+
+struct GemmShape {
+  int taps, N, K, kstep, pack_mode;
+};
+GemmShape gemm_shape(int op, int dir, int Cin, int Cout) {
+  const GemmKind k = gemm_kind(op, dir);
+  const int n = dir == 0 ? Cout : Cin;
+  return {k.ks * k.ks, k.scatter ? 4 * n : n, dir == 0 ? Cin : Cout, k.kstep, k.pack_mode};
+}
+
+// halfs of the image wp[tap][Np][Kp] the pack kernel writes and the GEMM kernel reads ALL of, 16 bytes at a time: Np = N rounded up to kTileN, Kp = K
+// rounded up to the K step.  For block-64 channel counts it is taps * Cin * Cout.
+size_t packed_halfs(const GemmShape& g) { return (size_t)g.taps * (size_t)padded(g.N, kTileN) * (size_t)padded(g.K, g.kstep); }
+
+// the weight gradient: taps of the filter itself (those of the data gradient's GEMM; the transpose forward folds its four into N), and the rows RH of
+// a pixel tile of its instantiation (LDS: 58.5 KB / 43.5 KB split-f16; the 1x1 has flat tiles)
+constexpr int taps_of(int op) { return gemm_kind(op, 1).ks * gemm_kind(op, 1).ks; }
+constexpr int wgrad_rows(int op) { return op == kOpConv3 ? 2 : 1; }
+
+// the implicit GEMM of (OP, DIR), instantiated from its gemm_kind.  H, W = the tile grid (the forward's input size); the input is `stride` times that.
+template <int PREC, bool RAGGED, int OP, int DIR>
+void launch_igemm(const GemmShape& g, const float* in, const uint16_t* wh, const uint16_t* wl, float* out, int B, int H, int W, hipStream_t st) {
+  constexpr GemmKind k = gemm_kind(OP, DIR);
+  const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
+  hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>),
+                     dim3((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)((g.N + kTileN - 1) / kTileN), (unsigned)B), dim3(kThreads), 0, st, in, wh,
+                     wl, out, g.K, g.N, k.stride * H, k.stride * W, H, W, tiles_x);
+}
+
+// RAGGED launches the guarded instantiations: grids round the channel blocks up, the packed image is the padded one (!RAGGED: no pad to add)
 template <int PREC, bool RAGGED>
 hipError_t launch_conv_prec(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
                             hipStream_t st) {
-  const size_t nw = packed_halfs(op, dir, Cin, Cout);      // (!RAGGED: taps * Cin * Cout)
+  const GemmShape g = gemm_shape(op, dir, Cin, Cout);
   uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
-  uint16_t* wl = wh + nw;      // (only the split mode reads or writes it)
+  uint16_t* wl = wh + packed_halfs(g);      // (only the split mode reads or writes it)
+  hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(packed_halfs(g))), dim3(kThreads), 0, st, w, wh, wl, g.pack_mode, g.N, g.K,
+                     g.taps, g.kstep);
   if (op == kOpConv1) {
-    const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin, P = H * W;
+    const int P = H * W;
     const unsigned ptiles = (unsigned)((P + kPwTile - 1) / kPwTile);
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl,
-                       dir == 0 ? kPackPwFwd : kPackPwBwd, N, K, 1, 32);
-    if (N % 128 == 0)      // four 32-channel blocks per wave where the channels allow: half the re-reads of the input
-      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 4, RAGGED>), dim3(ptiles * (unsigned)(N / 128), (unsigned)B), dim3(kThreads), 0, st, in,
-                         (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
+    if (g.N % 128 == 0)      // four 32-channel blocks per wave where the channels allow: half the re-reads of the input
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 4, RAGGED>), dim3(ptiles * (unsigned)(g.N / 128), (unsigned)B), dim3(kThreads), 0, st, in,
+                         (const uint16_t*)wh, (const uint16_t*)wl, out, g.K, g.N, P);
     else
-      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 2, RAGGED>), dim3(ptiles * (unsigned)((N + 63) / 64), (unsigned)B), dim3(kThreads), 0, st,
-                         in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, P);
-    return hipGetLastError();
-  }
-  const int tiles_x = (W + kTileW - 1) / kTileW, tiles_y = (H + kTileH - 1) / kTileH;
-  const unsigned tiles = (unsigned)tiles_x * (unsigned)tiles_y;
-  if (op == kOpConv3) {
-    const int K = dir == 0 ? Cin : Cout, N = dir == 0 ? Cout : Cin;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl,
-                       dir == 0 ? kPackConvFwd : kPackConvBwd, N, K, 9, 32);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 3, 1, 1, 32, false, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
-                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+      hipLaunchKernelGGL((dd_conv1x1_gemm_kernel<PREC, 2, RAGGED>), dim3(ptiles * (unsigned)((g.N + 63) / 64), (unsigned)B), dim3(kThreads), 0, st,
+                         in, (const uint16_t*)wh, (const uint16_t*)wl, out, g.K, g.N, P);
+  } else if (op == kOpConv3 && dir == 0) {      // (the 3x3's two directions are one instantiation: the pack mode alone tells them apart)
+    launch_igemm<PREC, RAGGED, kOpConv3, 0>(g, in, wh, wl, out, B, H, W, st);
+  } else if (op == kOpConv3) {
+    launch_igemm<PREC, RAGGED, kOpConv3, 1>(g, in, wh, wl, out, B, H, W, st);
   } else if (dir == 0) {
-    const int K = Cin, N = 4 * Cout;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvFwd, N, K, 1, 32);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 1, 1, 0, 32, true, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
-                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, H, W, H, W, tiles_x);
+    launch_igemm<PREC, RAGGED, kOpDeconv2, 0>(g, in, wh, wl, out, B, H, W, st);
   } else {
-    const int K = Cout, N = Cin;
-    hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(nw)), dim3(kThreads), 0, st, w, wh, wl, kPackDeconvBwd, N, K, 4, 16);
-    hipLaunchKernelGGL((dd_conv_igemm_kernel<PREC, 2, 2, 0, 16, false, RAGGED>), dim3(tiles, (unsigned)((N + kTileN - 1) / kTileN), (unsigned)B),
-                       dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl, out, K, N, 2 * H, 2 * W, H, W, tiles_x);
+    launch_igemm<PREC, RAGGED, kOpDeconv2, 1>(g, in, wh, wl, out, B, H, W, st);
   }
   return hipGetLastError();
 }
@@ -562,50 +596,41 @@ template <int PREC, bool RAGGED>
 hipError_t launch_wgrad_prec(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                              hipStream_t st) {
   const WgradSplit sp = wgrad_split(op, B, H, W);
-  const int tiles_x = (W + 31) / 32;
+  const int tiles_x = (W + 31) / 32, tiles_y = (H + wgrad_rows(op) - 1) / wgrad_rows(op);      // (the 1x1 has flat tiles: sp.tiles)
   float* part = reinterpret_cast<float*>(workspace);
   const dim3 grid((unsigned)(((Cin + 63) / 64) * ((Cout + 63) / 64)), (unsigned)sp.splits);
   if (op == kOpConv1) {
     hipLaunchKernelGGL((dd_conv1x1_wgrad_kernel<PREC, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H * W,
                        (H * W + kPwTile - 1) / kPwTile, (long long)sp.tiles, sp.tiles_per_split);
   } else if (op == kOpConv3) {
-    const int tiles_y = (H + kWgradRowsConv - 1) / kWgradRowsConv;
-    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, kWgradRowsConv, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, H, W,
-                       H, W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 1, 1, wgrad_rows(kOpConv3), RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin,
+                       H, W, H, W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
   } else {
-    const int tiles_y = (H + kWgradRowsDeconv - 1) / kWgradRowsDeconv;
-    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, kWgradRowsDeconv, RAGGED>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout, H,
-                       W, 2 * H, 2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 2, 2, 0, wgrad_rows(kOpDeconv2), RAGGED>), grid, dim3(kThreads), 0, st, x, grad_y, part, Cin, Cout,
+                       H, W, 2 * H, 2 * W, tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split);
   }
-  const size_t total = (size_t)Cin * Cout * (op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1);
+  const size_t total = (size_t)Cin * Cout * taps_of(op);
   hipLaunchKernelGGL(dd_conv_wgrad_reduce_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits);
   return hipGetLastError();
 }
 
-template <bool RAGGED>
-hipError_t launch_conv_ragged(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
-                              int prec, hipStream_t st) {
-  if (prec == kPrecBf16) return launch_conv_prec<kPrecBf16, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
-  if (prec == kPrecF16) return launch_conv_prec<kPrecF16, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
-  return launch_conv_prec<kPrecF16x3, RAGGED>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
-}
-
-template <bool RAGGED>
-hipError_t launch_wgrad_ragged(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
-                               int prec, hipStream_t st) {
-  if (prec == kPrecBf16) return launch_wgrad_prec<kPrecBf16, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
-  if (prec == kPrecF16) return launch_wgrad_prec<kPrecF16, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
-  return launch_wgrad_prec<kPrecF16x3, RAGGED>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+// f(precision, ragged) with the runtime operand mode and contract as the compile-time constants the kernels are instantiated with.  A shape of the
+// block-64 contract runs the block-64 instantiations, whichever entry point it came through; only the others run the guarded ones.
+template <class F>
+hipError_t dispatch(int prec, int Cin, int Cout, F f) {
+  const auto by_channels = [&](auto p) { return block64(Cin, Cout) ? f(p, std::false_type{}) : f(p, std::true_type{}); };
+  if (prec == kPrecBf16) return by_channels(std::integral_constant<int, kPrecBf16>{});
+  if (prec == kPrecF16) return by_channels(std::integral_constant<int, kPrecF16>{});
+  return by_channels(std::integral_constant<int, kPrecF16x3>{});
 }
 
 }  // namespace
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
 WgradSplit wgrad_split(int op, int B, int H, int W) {
-  const int rh = op == kOpConv3 ? kWgradRowsConv : kWgradRowsDeconv;
   WgradSplit s;
   if (op == kOpConv1) s.tiles = (int64_t)B * (((int64_t)H * W + kPwTile - 1) / kPwTile);      // flat tiles, none across an image
-  else s.tiles = (int64_t)B * ((H + rh - 1) / rh) * ((W + 31) / 32);
+  else s.tiles = (int64_t)B * ((H + wgrad_rows(op) - 1) / wgrad_rows(op)) * ((W + 31) / 32);
   int64_t per = (s.tiles + kMaxSplits - 1) / kMaxSplits;
   if (per < kSplitTiles) per = kSplitTiles;
   s.tiles_per_split = (int)per;
@@ -613,41 +638,30 @@ WgradSplit wgrad_split(int op, int B, int H, int W) {
   return s;
 }
 
-bool block64(int Cin, int Cout) {
-  return Cin >= 64 && Cin <= 1536 && Cin % 64 == 0 && Cout >= 64 && Cout <= 1536 && Cout % 64 == 0;
-}
+bool block64(int Cin, int Cout) { return channels_block64(Cin) && channels_block64(Cout); }
 
-// halfs of the packed image wp[tap][Np][Kp] of one direction: Np = N rounded up to kTileN, Kp = K rounded up to the K step of the GEMM kernel that
-// reads it (32; 16 for the transpose convolution's data gradient).  The GEMM kernels read ALL of it, 16 bytes at a time: this is the size the pack
-// kernel writes and the size workspace_bytes must cover.  For block-64 channel counts it is taps * Cin * Cout.
-size_t packed_halfs(int op, int dir, int Cin, int Cout) {
-  int taps, N, K, kstep = 32;
-  if (op == kOpDeconv2 && dir == 0) { taps = 1; N = 4 * Cout; K = Cin; }
-  else if (op == kOpDeconv2) { taps = 4; N = Cin; K = Cout; kstep = 16; }
-  else { taps = op == kOpConv3 ? 9 : 1; N = dir == 0 ? Cout : Cin; K = dir == 0 ? Cin : Cout; }
-  return (size_t)taps * (size_t)padded(N, kTileN) * (size_t)padded(K, kstep);
-}
+size_t packed_halfs(int op, int dir, int Cin, int Cout) { return packed_halfs(gemm_shape(op, dir, Cin, Cout)); }
 
 size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec) {
-  const size_t taps = op == kOpConv3 ? 9 : op == kOpDeconv2 ? 4 : 1;
   const size_t fwd = packed_halfs(op, 0, Cin, Cout), bwd = packed_halfs(op, 1, Cin, Cout);
   const size_t packed = (fwd > bwd ? fwd : bwd) * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);      // hi, and lo behind it in the split mode
-  const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * taps * (size_t)Cin * (size_t)Cout * sizeof(float);
+  const size_t partials = (size_t)wgrad_split(op, B, H, W).splits * (size_t)taps_of(op) * (size_t)Cin * (size_t)Cout * sizeof(float);
   const size_t need = packed > partials ? packed : partials;
   return (need + 255) / 256 * 256;
 }
 
-// a shape of the block-64 contract runs the block-64 instantiations, whichever entry point it came through; only the others run the guarded ones
 hipError_t launch_conv(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H, int W,
                        int prec, hipStream_t st) {
-  if (block64(Cin, Cout)) return launch_conv_ragged<false>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, prec, st);
-  return launch_conv_ragged<true>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, prec, st);
+  return dispatch(prec, Cin, Cout, [&](auto p, auto ragged) {
+    return launch_conv_prec<decltype(p)::value, decltype(ragged)::value>(op, dir, in, w, out, workspace, B, Cin, Cout, H, W, st);
+  });
 }
 
 hipError_t launch_wgrad(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                         int prec, hipStream_t st) {
-  if (block64(Cin, Cout)) return launch_wgrad_ragged<false>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, prec, st);
-  return launch_wgrad_ragged<true>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, prec, st);
+  return dispatch(prec, Cin, Cout, [&](auto p, auto ragged) {
+    return launch_wgrad_prec<decltype(p)::value, decltype(ragged)::value>(op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, st);
+  });
 }
 
 }  // namespace ddconv

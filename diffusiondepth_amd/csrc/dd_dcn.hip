@@ -17,32 +17,14 @@
 #include <hip/hip_runtime.h>
 
 #include "dd_gcn.h"
+#include "dd_status.h"
 
 #include <climits>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <string>
 
 namespace {
 
-thread_local std::string g_dcn_err;
-
-int dcn_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_dcn_err = buf;
-  return code;
-}
-
-#define DCN_HIP(expr)                                                                            \
-  do {                                                                                           \
-    hipError_t _e = (expr);                                                                      \
-    if (_e != hipSuccess) return dcn_fail(DD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
+thread_local ddstatus::LastError g_dcn_err;
 
 // ---- bilinear cell of one sampling position (mdmcn_im2col_bilinear, ...cuh:23-54, and the kernel's range test, ...cuh:179) ----
 struct Tap {
@@ -691,16 +673,16 @@ int check_dcn_args(DcnShape& s, int B, int C, int H, int W, int Cout, int kh, in
                    int group, int dg, int im2col_step) {
   if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || Cout <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || dh <= 0 || dw <= 0 || ph < 0 ||
       pw < 0 || group <= 0 || dg <= 0 || im2col_step <= 0)
-    return dcn_fail(DD_ERR_INVALID_ARG, "sizes, strides, dilations, groups and im2col_step must be positive (paddings non-negative)");
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "sizes, strides, dilations, groups and im2col_step must be positive (paddings non-negative)");
   const int step = B < im2col_step ? B : im2col_step;
   if (B % step != 0)                                           // modulated_deform_conv_cuda.cu:58
-    return dcn_fail(DD_ERR_INVALID_ARG, "batch(%d) must divide im2col_step(%d)", B, step);
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "batch(%d) must divide im2col_step(%d)", B, step);
   if (C % group != 0 || Cout % group != 0)                     // :60-61
-    return dcn_fail(DD_ERR_INVALID_ARG, "channels(%d) and channels_out(%d) must divide group(%d)", C, Cout, group);
-  if (C % dg != 0) return dcn_fail(DD_ERR_INVALID_ARG, "channels(%d) must divide deformable_group(%d)", C, dg);
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "channels(%d) and channels_out(%d) must divide group(%d)", C, Cout, group);
+  if (C % dg != 0) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "channels(%d) must divide deformable_group(%d)", C, dg);
   const int Ho = (H + 2 * ph - (dh * (kh - 1) + 1)) / sh + 1, Wo = (W + 2 * pw - (dw * (kw - 1) + 1)) / sw + 1;   // :75-76
   if (Ho <= 0 || Wo <= 0 || H + 2 * ph < dh * (kh - 1) + 1 || W + 2 * pw < dw * (kw - 1) + 1)
-    return dcn_fail(DD_ERR_INVALID_ARG, "empty output (%d x %d)", Ho, Wo);
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "empty output (%d x %d)", Ho, Wo);
   s = DcnShape{B, C, H, W, Cout, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw, group, dg};
   return DD_OK;
 }
@@ -762,7 +744,7 @@ int launch_prop(const float* fin, const float* offset, const float* aff, const f
     if (c.vec != 4 && !c.pair) hipLaunchKernelGGL((nlspn_prop_kernel<KF, 1, false>), grid, block, 0, st, DD_PROP_ARGS);
   }
 #undef DD_PROP_ARGS
-  DCN_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   return DD_OK;
 }
 
@@ -770,19 +752,19 @@ int launch_prop(const float* fin, const float* offset, const float* aff, const f
 
 extern "C" {
 
-const char* dd_dcn_last_error(void) { return g_dcn_err.c_str(); }
+const char* dd_dcn_last_error(void) { return g_dcn_err.text.c_str(); }
 
 int dd_dcn_forward(const float* input, const float* weight, const float* bias, const float* offset, const float* mask, float* output,
                    int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw, int group, int dg,
                    int im2col_step, void* stream) {
-  if (!input || !weight || !bias || !offset || !mask || !output) return dcn_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+  if (!input || !weight || !bias || !offset || !mask || !output) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
   DcnShape s;
   if (int rc = check_dcn_args(s, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, dg, im2col_step)) return rc;
   const size_t total = (size_t)B * Cout * s.Ho * s.Wo;
-  if (total > (size_t)INT_MAX * 256) return dcn_fail(DD_ERR_INVALID_ARG, "output too large");
+  if (total > (size_t)INT_MAX * 256) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "output too large");
   hipLaunchKernelGGL(dcn_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, input, weight, bias,
                      offset, mask, output, total);
-  DCN_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   return DD_OK;
 }
 
@@ -791,19 +773,19 @@ int dd_dcn_backward(const float* input, const float* weight, const float* bias, 
                     float* grad_bias, int B, int C, int H, int W, int Cout, int kh, int kw, int sh, int sw, int ph, int pw, int dh, int dw,
                     int group, int dg, int im2col_step, void* stream) {
   (void)bias;
-  if (!input || !weight || !offset || !mask || !grad_output) return dcn_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+  if (!input || !weight || !offset || !mask || !grad_output) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
   DcnShape s;
   if (int rc = check_dcn_args(s, B, C, H, W, Cout, kh, kw, sh, sw, ph, pw, dh, dw, group, dg, im2col_step)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const int K = kh * kw;
   const size_t npos = (size_t)B * s.Ho * s.Wo;
-  if (grad_input) DCN_HIP(hipMemsetAsync(grad_input, 0, (size_t)B * C * H * W * sizeof(float), st));
+  if (grad_input) DD_STATUS_HIP(g_dcn_err, hipMemsetAsync(grad_input, 0, (size_t)B * C * H * W * sizeof(float), st));
   if (grad_input || grad_offset || grad_mask) {
     const size_t total = npos * K * dg;
-    if (total > (size_t)INT_MAX * 256) return dcn_fail(DD_ERR_INVALID_ARG, "problem too large");
+    if (total > (size_t)INT_MAX * 256) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "problem too large");
     hipLaunchKernelGGL(dcn_bwd_data_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, s, input, weight, offset, mask,
                        grad_output, grad_input, grad_offset, grad_mask, total);
-    DCN_HIP(hipGetLastError());
+    DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   }
   // slabs of positions so that a one-channel NLSPN-sized problem (9 weight elements) still fills the chip
   size_t nslab = (npos + 8191) / 8192;
@@ -811,15 +793,15 @@ int dd_dcn_backward(const float* input, const float* weight, const float* bias, 
   const size_t slab = (npos + nslab - 1) / nslab;
   if (grad_weight) {
     const size_t nw = (size_t)Cout * (C / group) * K;
-    DCN_HIP(hipMemsetAsync(grad_weight, 0, nw * sizeof(float), st));
+    DD_STATUS_HIP(g_dcn_err, hipMemsetAsync(grad_weight, 0, nw * sizeof(float), st));
     hipLaunchKernelGGL(dcn_bwd_weight_kernel, dim3((unsigned)nw, (unsigned)nslab), dim3(256), 0, st, s, input, offset, mask, grad_output,
                        grad_weight, npos, slab);
-    DCN_HIP(hipGetLastError());
+    DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   }
   if (grad_bias) {
-    DCN_HIP(hipMemsetAsync(grad_bias, 0, (size_t)Cout * sizeof(float), st));
+    DD_STATUS_HIP(g_dcn_err, hipMemsetAsync(grad_bias, 0, (size_t)Cout * sizeof(float), st));
     hipLaunchKernelGGL(dcn_bwd_bias_kernel, dim3((unsigned)Cout, (unsigned)nslab), dim3(256), 0, st, s, grad_output, grad_bias, npos, slab);
-    DCN_HIP(hipGetLastError());
+    DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   }
   return DD_OK;
 }
@@ -827,11 +809,11 @@ int dd_dcn_backward(const float* input, const float* weight, const float* bias, 
 int dd_nlspn_offset_affinity(const float* offset_aff, const float* confidence, const float* aff_scale_const, const float* w_conf,
                              const float* b_conf, float* offset, float* aff, int B, int H, int W, int k_f, int affinity, int conf_prop,
                              int legacy, void* stream) {
-  if (!offset_aff || !aff_scale_const || !offset || !aff) return dcn_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
-  if (B <= 0 || H <= 0 || W <= 0) return dcn_fail(DD_ERR_INVALID_ARG, "B, H, W must be positive");
-  if (affinity < DD_AFF_AS || affinity > DD_AFF_TGASS) return dcn_fail(DD_ERR_INVALID_ARG, "unknown affinity mode %d", affinity);
+  if (!offset_aff || !aff_scale_const || !offset || !aff) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+  if (B <= 0 || H <= 0 || W <= 0) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "B, H, W must be positive");
+  if (affinity < DD_AFF_AS || affinity > DD_AFF_TGASS) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "unknown affinity mode %d", affinity);
   if (conf_prop && (!confidence || !w_conf || !b_conf))                     // `assert confidence is not None`, nlspnmodel.py:180
-    return dcn_fail(DD_ERR_INVALID_ARG, "conf_prop needs confidence, w_conf and b_conf");
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "conf_prop needs confidence, w_conf and b_conf");
   const float* conf = conf_prop ? confidence : nullptr;
   const dim3 grid((W + 63) / 64, (H + 3) / 4, B), block(64, 4);
   hipStream_t st = (hipStream_t)stream;
@@ -839,31 +821,31 @@ int dd_nlspn_offset_affinity(const float* offset_aff, const float* confidence, c
     case 3: hipLaunchKernelGGL(nlspn_affinity_kernel<3>, grid, block, 0, st, offset_aff, conf, aff_scale_const, w_conf, b_conf, offset, aff, H, W, affinity, legacy); break;
     case 5: hipLaunchKernelGGL(nlspn_affinity_kernel<5>, grid, block, 0, st, offset_aff, conf, aff_scale_const, w_conf, b_conf, offset, aff, H, W, affinity, legacy); break;
     case 7: hipLaunchKernelGGL(nlspn_affinity_kernel<7>, grid, block, 0, st, offset_aff, conf, aff_scale_const, w_conf, b_conf, offset, aff, H, W, affinity, legacy); break;
-    default: return dcn_fail(DD_ERR_UNSUPPORTED, "prop_kernel %d: this build has 3, 5 and 7 (the reference asserts an odd size, nlspnmodel.py:35)", k_f);
+    default: return g_dcn_err.fail(DD_ERR_UNSUPPORTED, "prop_kernel %d: this build has 3, 5 and 7 (the reference asserts an odd size, nlspnmodel.py:35)", k_f);
   }
-  DCN_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   return DD_OK;
 }
 
 int dd_nlspn_guided_offset_affinity(const float* guidance, const float* conv_weight, const float* conv_bias, const float* confidence,
                                     const float* aff_scale_const, const float* w_conf, const float* b_conf, float* offset, float* aff,
                                     int B, int ch_g, int H, int W, int k_g, int k_f, int affinity, int conf_prop, int legacy, void* stream) {
-  if (!guidance || !conv_weight || !conv_bias || !aff_scale_const || !offset || !aff) return dcn_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
-  if (B <= 0 || H <= 0 || W <= 0) return dcn_fail(DD_ERR_INVALID_ARG, "B, H, W must be positive");
-  if (affinity < DD_AFF_AS || affinity > DD_AFF_TGASS) return dcn_fail(DD_ERR_INVALID_ARG, "unknown affinity mode %d", affinity);
-  if (conf_prop && (!confidence || !w_conf || !b_conf)) return dcn_fail(DD_ERR_INVALID_ARG, "conf_prop needs confidence, w_conf and b_conf");
+  if (!guidance || !conv_weight || !conv_bias || !aff_scale_const || !offset || !aff) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+  if (B <= 0 || H <= 0 || W <= 0) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "B, H, W must be positive");
+  if (affinity < DD_AFF_AS || affinity > DD_AFF_TGASS) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "unknown affinity mode %d", affinity);
+  if (conf_prop && (!confidence || !w_conf || !b_conf)) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "conf_prop needs confidence, w_conf and b_conf");
   if (ch_g != 8 || k_g != 3 || k_f != 3)
-    return dcn_fail(DD_ERR_UNSUPPORTED, "fused guidance convolution is built for ch_g 8, k_g 3, k_f 3 (NLSPNModel's geometry); got %d, %d, %d: "
+    return g_dcn_err.fail(DD_ERR_UNSUPPORTED, "fused guidance convolution is built for ch_g 8, k_g 3, k_f 3 (NLSPNModel's geometry); got %d, %d, %d: "
                                         "run the convolution separately and call dd_nlspn_offset_affinity", ch_g, k_g, k_f);
   const dim3 grid((W + 63) / 64, (H + 7) / 8, B), block(256);
   hipLaunchKernelGGL(nlspn_guide_affinity_kernel<8>, grid, block, 0, (hipStream_t)stream, guidance, conv_weight, conv_bias,
                      conf_prop ? confidence : nullptr, aff_scale_const, w_conf, b_conf, offset, aff, H, W, affinity, legacy);
-  DCN_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   return DD_OK;
 }
 
 int dd_nlspn_workspace_bytes(int B, int H, int W, int preserve_input, int64_t* bytes) {
-  if (!bytes || B <= 0 || H <= 0 || W <= 0) return dcn_fail(DD_ERR_INVALID_ARG, "bad arguments");
+  if (!bytes || B <= 0 || H <= 0 || W <= 0) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "bad arguments");
   *bytes = preserve_input ? (int64_t)2 * B * H * W * (int64_t)sizeof(float) : 0;
   return DD_OK;
 }
@@ -871,12 +853,12 @@ int dd_nlspn_workspace_bytes(int B, int H, int W, int preserve_input, int64_t* b
 int dd_nlspn_propagate(const float* feat_init, const float* offset, const float* aff, const float* feat_fix, const float* w,
                        const float* b, float* feat_list, void* workspace, int B, int H, int W, int k_f, int prop_time,
                        int preserve_input, void* stream) {
-  if (!feat_init || !offset || !aff || !w || !b || !feat_list) return dcn_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
-  if (B <= 0 || H <= 0 || W <= 0 || prop_time <= 0) return dcn_fail(DD_ERR_INVALID_ARG, "B, H, W, prop_time must be positive");
+  if (!feat_init || !offset || !aff || !w || !b || !feat_list) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+  if (B <= 0 || H <= 0 || W <= 0 || prop_time <= 0) return g_dcn_err.fail(DD_ERR_INVALID_ARG, "B, H, W, prop_time must be positive");
   if (preserve_input && (!feat_fix || !workspace))                          // `assert feat_init.shape == feat_fix.shape`, nlspnmodel.py:188
-    return dcn_fail(DD_ERR_INVALID_ARG, "preserve_input needs feat_fix and a workspace of dd_nlspn_workspace_bytes()");
+    return g_dcn_err.fail(DD_ERR_INVALID_ARG, "preserve_input needs feat_fix and a workspace of dd_nlspn_workspace_bytes()");
   if (k_f != 3 && k_f != 5 && k_f != 7)
-    return dcn_fail(DD_ERR_UNSUPPORTED, "prop_kernel %d: this build has 3, 5 and 7", k_f);
+    return g_dcn_err.fail(DD_ERR_UNSUPPORTED, "prop_kernel %d: this build has 3, 5 and 7", k_f);
   hipStream_t st = (hipStream_t)stream;
   const size_t n = (size_t)B * H * W;
   float* ws[2] = {nullptr, nullptr};
@@ -884,7 +866,7 @@ int dd_nlspn_propagate(const float* feat_init, const float* offset, const float*
     ws[0] = static_cast<float*>(workspace);
     ws[1] = ws[0] + n;
     hipLaunchKernelGGL(nlspn_blend_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, feat_init, feat_fix, ws[0], n);
-    DCN_HIP(hipGetLastError());
+    DD_STATUS_HIP(g_dcn_err, hipGetLastError());
   }
   for (int it = 0; it < prop_time; ++it) {
     const float* fin = preserve_input ? ws[it & 1] : (it == 0 ? feat_init : feat_list + (size_t)(it - 1) * n);

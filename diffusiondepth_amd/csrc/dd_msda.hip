@@ -13,31 +13,14 @@
 
 #include <hip/hip_runtime.h>
 
+#include "dd_status.h"
+
 #include <climits>
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
-#include <string>
 
 namespace {
 
-thread_local std::string g_msda_err;
-
-int msda_fail(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_msda_err = buf;
-  return code;
-}
-
-#define MSDA_HIP(expr)                                                                            \
-  do {                                                                                            \
-    hipError_t _e = (expr);                                                                       \
-    if (_e != hipSuccess) return msda_fail(DD_ERR_HIP, "%s: %s", #expr, hipGetErrorString(_e));   \
-  } while (0)
+thread_local ddstatus::LastError g_msda_err;
 
 struct MsdaShape { int B, K, M, D, L, Q, P; };
 
@@ -200,10 +183,10 @@ __global__ void __launch_bounds__(256) msda_bwd_kernel(MsdaShape s, const float*
 
 int check_msda(MsdaShape& s, int B, int K, int M, int D, int L, int Q, int P, int im2col_step) {
   if (B <= 0 || K <= 0 || M <= 0 || D <= 0 || L <= 0 || Q <= 0 || P <= 0 || im2col_step <= 0)
-    return msda_fail(DD_ERR_INVALID_ARG, "sizes and im2col_step must be positive");
+    return g_msda_err.fail(DD_ERR_INVALID_ARG, "sizes and im2col_step must be positive");
   const int step = B < im2col_step ? B : im2col_step;
-  if (B % step != 0) return msda_fail(DD_ERR_INVALID_ARG, "batch(%d) must divide im2col_step(%d)", B, step);
-  if ((long long)B * Q * M * D > (long long)INT_MAX * 256) return msda_fail(DD_ERR_INVALID_ARG, "output too large");
+  if (B % step != 0) return g_msda_err.fail(DD_ERR_INVALID_ARG, "batch(%d) must divide im2col_step(%d)", B, step);
+  if ((long long)B * Q * M * D > (long long)INT_MAX * 256) return g_msda_err.fail(DD_ERR_INVALID_ARG, "output too large");
   s = MsdaShape{B, K, M, D, L, Q, P};
   return DD_OK;
 }
@@ -212,13 +195,13 @@ int check_msda(MsdaShape& s, int B, int K, int M, int D, int L, int Q, int P, in
 
 extern "C" {
 
-const char* dd_msda_last_error(void) { return g_msda_err.c_str(); }
+const char* dd_msda_last_error(void) { return g_msda_err.text.c_str(); }
 
 int dd_msda_forward(const float* value, const int64_t* spatial_shapes, const int64_t* level_start_index, const float* sampling_locations,
                     const float* attention_weights, float* out, int B, int num_keys, int M, int D, int L, int Q, int P, int im2col_step,
                     void* stream) {
   if (!value || !spatial_shapes || !level_start_index || !sampling_locations || !attention_weights || !out)
-    return msda_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+    return g_msda_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
   MsdaShape s;
   if (int rc = check_msda(s, B, num_keys, M, D, L, Q, P, im2col_step)) return rc;
   const long long total = (long long)B * Q * M * D;
@@ -229,7 +212,7 @@ int dd_msda_forward(const float* value, const int64_t* spatial_shapes, const int
   else
     hipLaunchKernelGGL(msda_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, s, value, spatial_shapes,
                        level_start_index, sampling_locations, attention_weights, out, total);
-  MSDA_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_msda_err, hipGetLastError());
   return DD_OK;
 }
 
@@ -237,14 +220,14 @@ int dd_msda_backward(const float* value, const int64_t* spatial_shapes, const in
                      const float* attention_weights, const float* grad_out, float* grad_value, float* grad_sampling_loc,
                      float* grad_attn_weight, int B, int num_keys, int M, int D, int L, int Q, int P, int im2col_step, void* stream) {
   if (!value || !spatial_shapes || !level_start_index || !sampling_locations || !attention_weights || !grad_out)
-    return msda_fail(DD_ERR_INVALID_ARG, "null tensor pointer");
+    return g_msda_err.fail(DD_ERR_INVALID_ARG, "null tensor pointer");
   MsdaShape s;
   if (int rc = check_msda(s, B, num_keys, M, D, L, Q, P, im2col_step)) return rc;
   hipStream_t st = (hipStream_t)stream;
   const size_t nsamp = (size_t)B * Q * M * L * P;
-  if (grad_value) MSDA_HIP(hipMemsetAsync(grad_value, 0, (size_t)B * num_keys * M * D * sizeof(float), st));
-  if (grad_sampling_loc) MSDA_HIP(hipMemsetAsync(grad_sampling_loc, 0, nsamp * 2 * sizeof(float), st));
-  if (grad_attn_weight) MSDA_HIP(hipMemsetAsync(grad_attn_weight, 0, nsamp * sizeof(float), st));
+  if (grad_value) DD_STATUS_HIP(g_msda_err, hipMemsetAsync(grad_value, 0, (size_t)B * num_keys * M * D * sizeof(float), st));
+  if (grad_sampling_loc) DD_STATUS_HIP(g_msda_err, hipMemsetAsync(grad_sampling_loc, 0, nsamp * 2 * sizeof(float), st));
+  if (grad_attn_weight) DD_STATUS_HIP(g_msda_err, hipMemsetAsync(grad_attn_weight, 0, nsamp * sizeof(float), st));
   if (!grad_value && !grad_sampling_loc && !grad_attn_weight) return DD_OK;
   const long long total = (long long)B * Q * M * D;
   const dim3 grid((unsigned)((total + 255) / 256)), block(256);
@@ -263,7 +246,7 @@ int dd_msda_backward(const float* value, const int64_t* spatial_shapes, const in
     default: MSDA_BWD(1); break;
   }
 #undef MSDA_BWD
-  MSDA_HIP(hipGetLastError());
+  DD_STATUS_HIP(g_msda_err, hipGetLastError());
   return DD_OK;
 }
 
