@@ -133,6 +133,7 @@ int dd_set_option(dd_handle_t h, const char* key, int64_t value) {
   else if (k == "naive_wgrad") h->naive_wgrad = value != 0;
   else if (k == "lane_probe") h->lane_probe = value != 0;
   else if (k == "x3_grad_fp32") h->x3_grad_fp32 = value != 0;
+  else if (k == "grad_autoscale") h->grad_autoscale = value != 0;
   else if (k == "keep_trajectory") h->keep_traj = value != 0;
   else if (k == "use_trajectory") h->use_traj = value;
   else if (k == "adjoint_tiled") h->adjoint_tiled = value != 0;

@@ -265,12 +265,17 @@ struct dd_handle_s {
   bool adjoint_tiled = true;  // Swin backward: tiled separable kernel for the adjoint of the condition upsampling (0 = the one-thread-per-piece kernel, A/B check)
   int64_t traj_serial = 0, use_traj = 0, weights_serial = 0, n_traj_reuse = 0;
   int naive_wgrad = 0;        // backward: 1 = weight gradients by the unfused kernel in every mode (A/B check of dd_wgrad.hip)
+  int grad_autoscale = 1;     // backward with f16 gradients (DD_PREC_F16, DD_PREC_F16X3 without "x3_grad_fp32"): 1 = the incoming gradient enters scaled by a power of two
+                              // taken from its largest finite magnitude (one per call, found on the device) and every result is unscaled on its way out; 0 = as it comes
+  DevBuf grad_scale;          // ... {s, 1/s, scratch} of the running call (launch_grad_scale)
   int x3_grad_fp32 = 0;       // DD_PREC_F16X3's backward: 0 = f16 gradients behind the split forward (the f16 mode's MFMA kernels), 1 = fp32 gradients (the fp32 mode's kernels)
   std::map<PlanKey, std::unique_ptr<Plan>> plans;
   DevBuf wgrad_ws[MAX_LANES]; // per-slab partial weight gradients of dd_wgrad.hip (one workspace per concurrent lane)
   // parameter gradients (fp32, reference shapes), accumulated like torch .grad in set 0; sets 1.. are the scratch of the concurrent lanes of
-  // dd_denoise_backward (added into set 0 and cleared at the join)
-  std::map<std::string, std::unique_ptr<DevBuf>> grads[MAX_LANES];
+  // dd_denoise_backward (added into set 0 and cleared at the join); set SCALED_SET takes what lane 0 (or a single call) computes from a SCALED
+  // incoming gradient (grad_autoscale): joined into set 0 with the factor 1/s, so set 0 never holds scaled values
+  static constexpr int SCALED_SET = MAX_LANES, GRAD_SETS = MAX_LANES + 1;
+  std::map<std::string, std::unique_ptr<DevBuf>> grads[GRAD_SETS];
   std::map<std::tuple<int, int, int, int, int>, std::pair<std::shared_ptr<DevBuf>, uint64_t>> cond_bufs;   // (B, h, w, precision, lane) -> buffer, last use
   // condition FPN (Res variant): folded + packed weights, workspace of the last shape, and where its result lives
   bool neck_committed = false;            // hahineck.* folded + packed (DD_VARIANT_SWIN with the Swin-L pyramid only)
@@ -373,9 +378,11 @@ void drain_layer_events(dd_handle_t h);
 float* grad_buf(dd_handle_t h, const std::string& name, size_t numel, hipStream_t s, hipError_t* err, int lane = 0);
 int ensure_bwd_buffers(dd_handle_t h, Plan* pl);
 int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, int t_base, int t_bstride, float* grad_cond,
-             int accumulate_cond, hipStream_t s, const Plan* kept = nullptr, int kstep = 0, int lane = 0);
+             int accumulate_cond, hipStream_t s, const Plan* kept = nullptr, int kstep = 0, int lane = 0, int gset = -1);
+int grad_scale_begin(dd_handle_t h, int precision, const float* g, long long n, hipStream_t s, const float** pair);
+int grad_scale_join(dd_handle_t h, int n_lanes, hipStream_t s);
 int check_bwd(dd_handle_t h, int precision, const char* who);
 int denoise_backward_lane(dd_handle_t h, const float* x_T, const float* cond, const float* grad_x0, float* grad_xT, float* grad_cond,
                           int B, int lat_h, int lat_w, int cond_h, int cond_w, int T, int precision, hipStream_t s, int lane, int img0,
-                          int whole_B, int64_t ticket, bool* reused, int S);
+                          int whole_B, int64_t ticket, bool* reused, int S, const float* gpair = nullptr);
 }  // namespace ddapi

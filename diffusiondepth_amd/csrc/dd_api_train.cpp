@@ -22,7 +22,7 @@ extern "C" {
 int dd_zero_grad(dd_handle_t h, void* stream) {
   if (!h) return DD_ERR_INVALID_ARG;
   DD_HIP(hipSetDevice(h->device));
-  for (int l = 0; l < dd_handle_s::MAX_LANES; ++l)      // set 0 = what dd_get_grad reads; sets 1.. = lane scratch (zero unless a call failed midway)
+  for (int l = 0; l < dd_handle_s::GRAD_SETS; ++l)      // set 0 = what dd_get_grad reads; sets 1.. = lane / scaled-call scratch (zero unless a call failed midway)
     for (auto& kv : h->grads[l]) DD_HIP(hipMemsetAsync(kv.second->p, 0, kv.second->bytes, reinterpret_cast<hipStream_t>(stream)));
   return DD_OK;
 }
@@ -40,6 +40,33 @@ int dd_get_grad(dd_handle_t h, const char* name, float* dst, int64_t numel, void
 
 }  // extern "C"
 namespace ddapi {
+
+// Option "grad_autoscale" (default on), for the calls whose gradients travel as f16 (bwd_core: ek == EK_F16): f16 goes subnormal below 6.1e-5 and
+// ends at 65504, and the gradient of a mean over millions of pixels sits around 2^-22 -- so the incoming gradient g (all images of the call) is
+// multiplied by a power of two s on its way in and everything the call hands back by 1/s.  *pair = {s, 1/s} on the device (launch_grad_scale: no host
+// read), or NULL where the call runs as it always did: fp32, bf16, "x3_grad_fp32", the option at 0.
+int grad_scale_begin(dd_handle_t h, int precision, const float* g, long long n, hipStream_t s, const float** pair) {
+  *pair = nullptr;
+  const int mode = ek_of_precision(precision, h->bf16_pure);
+  const bool f16_grads = precision != DD_PREC_NAIVE_FP32 && (mode == EK_F16S ? !h->x3_grad_fp32 : opnd_kind(mode) == EK_F16);
+  if (!h->grad_autoscale || !f16_grads) return DD_OK;
+  if (!h->grad_scale.p) DD_HIP(h->grad_scale.alloc(4 * sizeof(float)));
+  DD_HIP(launch_grad_scale(g, n, h->grad_scale.as<float>(), s));
+  *pair = h->grad_scale.as<float>();
+  return DD_OK;
+}
+// ... and at the end of such a call, on the caller's stream after the lanes joined: set 0 += (1/s) x set l, set l = 0, for the scaled set and the lane sets
+int grad_scale_join(dd_handle_t h, int n_lanes, hipStream_t s) {
+  for (int i = 0; i < n_lanes; ++i) {
+    const int l = i == 0 ? (int)dd_handle_s::SCALED_SET : i;
+    for (auto& kv : h->grads[l]) {
+      hipError_t e = hipSuccess;
+      float* dst = grad_buf(h, kv.first, kv.second->bytes / 4, s, &e, 0); DD_HIP(e);
+      DD_HIP(launch_add_scaled_clear(dst, kv.second->as<float>(), h->grad_scale.as<float>() + 1, (long long)(kv.second->bytes / 4), s));
+    }
+  }
+  return DD_OK;
+}
 
 int ensure_bwd_buffers(dd_handle_t h, Plan* pl) {
   if (pl->gA.p) return DD_OK;
@@ -62,7 +89,8 @@ int ensure_bwd_buffers(dd_handle_t h, Plan* pl) {
 // (fp32 NHWC16).  Recomputes the forward pass (GroupNorm sums in stat slot 0), accumulates the parameter gradients into
 // h->grads, writes (or accumulates) dLoss/dcond as NCHW fp32 into grad_cond when that is not NULL.
 int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, int t_base, int t_bstride, float* grad_cond,
-             int accumulate_cond, hipStream_t s, const Plan* kept, int kstep, int lane) {
+             int accumulate_cond, hipStream_t s, const Plan* kept, int kstep, int lane, int gset) {
+  if (gset < 0) gset = lane;                // the gradient set the parameter gradients go to (a scaled call's lane 0: dd_handle_s::SCALED_SET)
   // kept != NULL: the forward pass of this step is NOT recomputed -- its raw conv outputs and GroupNorm sums are read from slot `kstep`
   // of the forward plan that kept them (PlanKey::keep == 2; same shape and element kinds as `pl`)
   const Plan* src = kept ? kept : pl;
@@ -155,9 +183,9 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
     const ActView yv{ybuf[l], ek_y, lay, C, HW}, gav{pl->gA.p, (l == 3) ? (int)EK_F32 : ek_g, lay, C, HW}, gyv{pl->gY.p, ek_g, lay, C, HW};
     const float* gamma = h->L[l].gamma.as<float>();
     const float* beta = h->L[l].beta.as<float>();
-    float* dgam = grad_buf(h, std::string(kGnNames[l]) + ".weight", C, s, &e, lane); DD_HIP(e);
-    float* dbet = grad_buf(h, std::string(kGnNames[l]) + ".bias", C, s, &e, lane); DD_HIP(e);
-    float* dbias = grad_buf(h, std::string(kConvNames[l]) + ".bias", C, s, &e, lane); DD_HIP(e);
+    float* dgam = grad_buf(h, std::string(kGnNames[l]) + ".weight", C, s, &e, gset); DD_HIP(e);
+    float* dbet = grad_buf(h, std::string(kGnNames[l]) + ".bias", C, s, &e, gset); DD_HIP(e);
+    float* dbias = grad_buf(h, std::string(kConvNames[l]) + ".bias", C, s, &e, gset); DD_HIP(e);
     // 16-bit channel-blocked tensors (layers 0..2 of the fused bf16 / f16 modes): vectorised kernels, one pass for all sums
     const bool vec = !naive && ek != EK_F32 && l < 3;
     if (vec) {
@@ -166,7 +194,7 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
       DD_HIP(launch_gn_bwd_apply_blocked(pl->gA.p, ybuf[l], ek, yk, st(l), gamma, beta, pl->dgb.as<double>(), pl->gY.p, nullptr,
                                          nullptr, nullptr, nullptr, 0, 0, B, C, HW, s));
       float* demb = nullptr;
-      if (l == 1) { demb = grad_buf(h, "model.time_embedding.weight", (size_t)EMB_ROWS * COND_C, s, &e, lane); DD_HIP(e); }
+      if (l == 1) { demb = grad_buf(h, "model.time_embedding.weight", (size_t)EMB_ROWS * COND_C, s, &e, gset); DD_HIP(e); }
       DD_HIP(launch_gn_param_grad4(pl->dgb.as<double>(), st(l), gamma, dgam, dbet, dbias, demb, tv, t_base, t_bstride, B, C, HW, s));
     } else {
       DD_HIP(hipMemsetAsync(pl->dgb.p, 0, (size_t)B * C * 2 * sizeof(double), s));
@@ -178,7 +206,7 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
     rc = chk("GroupNorm-backward sums (dgb)", l, pl->dgb.p, (long long)B * C * (vec ? 4 : 2), 3); if (rc) return rc;
     rc = chk("dLoss/dy (gY)", l, pl->gY.p, (long long)B * C * HW, naive ? 0 : kk); if (rc) return rc;
     rc = chk("the conv's input activation", l, inbuf[l], (long long)B * CI * HW, naive ? 0 : kk); if (rc) return rc;
-    float* dw = grad_buf(h, std::string(kConvNames[l]) + ".weight", (size_t)C * CI * 9, s, &e, lane); DD_HIP(e);
+    float* dw = grad_buf(h, std::string(kConvNames[l]) + ".weight", (size_t)C * CI * 9, s, &e, gset); DD_HIP(e);
     const ActView inv{inbuf[l], ek_g, lay, CI, HW};
     if (!naive && ek != EK_F32 && !h->naive_wgrad) {
       const size_t need = wgrad_workspace_bytes(C, CI, B, lat_h, lat_w);
@@ -207,8 +235,8 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
       void* gbuf[3] = {pl->gA.p, pl->gY.p, pl->gA.p};      // gradient w.r.t. sf -> sa -> u
       for (int i = 0; i < 2; ++i) {
         const ActView gout{gbuf[i], ek, 1, COND_C, HW}, fv{fin[i], ek, 1, COND_C, HW};
-        float* db = grad_buf(h, std::string(fuse[i]) + ".bias", COND_C, s, &e, lane); DD_HIP(e);
-        float* dwf = grad_buf(h, std::string(fuse[i]) + ".weight", (size_t)COND_C * COND_C * 9, s, &e, lane); DD_HIP(e);
+        float* db = grad_buf(h, std::string(fuse[i]) + ".bias", COND_C, s, &e, gset); DD_HIP(e);
+        float* dwf = grad_buf(h, std::string(fuse[i]) + ".weight", (size_t)COND_C * COND_C * 9, s, &e, gset); DD_HIP(e);
         if (ek != EK_F32) DD_HIP(launch_channel_sum_blocked(gbuf[i], ek, db, B, COND_C, HW, s));
         else DD_HIP(launch_channel_sum(gout, db, nullptr, 0, 0, B, s));
         if (ek != EK_F32 && !h->naive_wgrad) {
@@ -235,7 +263,7 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
         else DD_HIP(launch_view_to_nchw(gf, grad_cond, B, accumulate_cond, s));
       }
       if (naive || ek == EK_F32) {     // (16-bit modes: the layer-1 reduction pass below also sums g_f per channel)
-        float* demb = grad_buf(h, "model.time_embedding.weight", (size_t)EMB_ROWS * COND_C, s, &e, lane); DD_HIP(e);
+        float* demb = grad_buf(h, "model.time_embedding.weight", (size_t)EMB_ROWS * COND_C, s, &e, gset); DD_HIP(e);
         DD_HIP(launch_channel_sum(gf, demb, tv, t_base, t_bstride, B, s));
       }
     }
@@ -295,6 +323,11 @@ int dd_denoise_once_backward(dd_handle_t h, const float* x_t, const int64_t* t, 
   rc = stage_condition(h, pl, cond, B, lat_h, lat_w, cond_h, cond_w, precision, s);
   if (rc) return rc;
   DD_HIP(launch_nchw_to_nhwc(grad_eps, pl->gA.p, EK_F32, B, LATENT_C, lat_h, lat_w, 0, s));
+  const float* gpair = nullptr;
+  const long long n_eps = (long long)B * LATENT_C * lat_h * lat_w;
+  rc = grad_scale_begin(h, precision, grad_eps, n_eps, s, &gpair);
+  if (rc) return rc;
+  if (gpair) DD_HIP(launch_scale_by(pl->gA.as<float>(), gpair, n_eps, s));
   // the forward call's activations, if it kept them for us (option "use_trajectory" = its ticket): no recompute
   const int64_t ticket = h->use_traj;
   h->use_traj = 0;
@@ -306,9 +339,18 @@ int dd_denoise_once_backward(dd_handle_t h, const float* x_t, const int64_t* t, 
   }
   if (kept) h->n_traj_reuse++;
   rc = check_finite_begin(h, s); if (rc) return rc;
-  rc = bwd_core(h, pl, pl->x[0].as<float>(), reinterpret_cast<const long long*>(t), 0, 1, grad_cond, 0, s, kept, 0);
-  if (rc) return rc;
+  rc = bwd_core(h, pl, pl->x[0].as<float>(), reinterpret_cast<const long long*>(t), 0, 1, grad_cond, 0, s, kept, 0, 0, gpair ? (int)dd_handle_s::SCALED_SET : 0);
+  if (rc) {
+    for (auto& kv : h->grads[dd_handle_s::SCALED_SET]) (void)hipMemsetAsync(kv.second->p, 0, kv.second->bytes, s);      // (no partial sums for the next call's join)
+    return rc;
+  }
   if (grad_x) DD_HIP(launch_nhwc_to_nchw_f32(pl->gA.p, EK_F32, grad_x, B, LATENT_C, lat_h, lat_w, 0, s));
+  if (gpair) {
+    if (grad_x) DD_HIP(launch_scale_by(grad_x, gpair + 1, n_eps, s));
+    if (grad_cond) DD_HIP(launch_scale_by(grad_cond, gpair + 1, (long long)B * COND_C * cond_h * cond_w, s));
+    rc = grad_scale_join(h, 1, s);
+    if (rc) return rc;
+  }
   h->last_once_plan = pl;
   return check_finite_report(h, s);
 }
@@ -319,7 +361,7 @@ namespace ddapi {
 // The loop backward on B images (a whole call or one lane of it, see denoise_lane); parameter gradients go to gradient set `lane`.
 int denoise_backward_lane(dd_handle_t h, const float* x_T, const float* cond, const float* grad_x0, float* grad_xT, float* grad_cond,
                           int B, int lat_h, int lat_w, int cond_h, int cond_w, int T, int precision, hipStream_t s, int lane, int img0,
-                          int whole_B, int64_t ticket, bool* reused, int S) {
+                          int whole_B, int64_t ticket, bool* reused, int S, const float* gpair) {
   int rc = DD_OK;
   Plan* pl = nullptr;
   rc = get_plan(h, PlanKey{B, lat_h, lat_w, cond_h, cond_w, T, precision, want_hoist(h, precision, T, 1), 0, lane, S}, &pl);      // recompute = the kernels of the forward that kept the trajectory
@@ -369,14 +411,19 @@ int denoise_backward_lane(dd_handle_t h, const float* x_T, const float* cond, co
     if (rc) return rc;
   }
   // ---- backward through the chain x_{k+1} = c1_k x_k + c2_k eps(x_k, t_k, cond) ----
+  // gpair != NULL (grad_autoscale): the running gradient G, and with it every step's gA and the accumulated grad_cond, carry the call's scale s
   DD_HIP(launch_nchw_to_nhwc(grad_x0, G, EK_F32, B, LATENT_C, lat_h, lat_w, 0, s));
+  if (gpair) DD_HIP(launch_scale_by(G, gpair, (long long)n16, s));
+  const int gset = (gpair && lane == 0) ? (int)dd_handle_s::SCALED_SET : lane;
   for (int k = T - 1; k >= 0; --k) {
     DD_HIP(launch_bwd_chain(G, pl->gA.as<float>(), pl->c1c2.as<float>(), k, 0, (long long)n16, s));          // gA = c2_k G
-    rc = bwd_core(h, pl, X + (size_t)k * n16, ts, k, 0, grad_cond, k < T - 1 ? 1 : 0, s, kept_act, k, lane);
+    rc = bwd_core(h, pl, X + (size_t)k * n16, ts, k, 0, grad_cond, k < T - 1 ? 1 : 0, s, kept_act, k, lane, gset);
     if (rc) return rc;
     DD_HIP(launch_bwd_chain(G, pl->gA.as<float>(), pl->c1c2.as<float>(), k, 1, (long long)n16, s));          // G = c1_k G + gA
   }
   if (grad_xT) DD_HIP(launch_nhwc_to_nchw_f32(G, EK_F32, grad_xT, B, LATENT_C, lat_h, lat_w, 0, s));
+  if (gpair && grad_xT) DD_HIP(launch_scale_by(grad_xT, gpair + 1, (long long)n16, s));
+  if (gpair && grad_cond) DD_HIP(launch_scale_by(grad_cond, gpair + 1, (long long)B * COND_C * cond_h * cond_w, s));
   return DD_OK;
 }
 }  // namespace ddapi
@@ -399,11 +446,21 @@ int dd_denoise_backward(dd_handle_t h, const float* x_T, const float* cond, cons
   // own gradient set and weight-gradient workspace, the sets of lanes 1.. are added into set 0 (what dd_get_grad reads) after the join.
   const int S = lane_count(h, B, precision);
   bool reused = false;
+  // one scale for the whole call, found over all images in front of the fork: per-image results do not depend on the number of lanes
+  const float* gpair = nullptr;
+  rc = grad_scale_begin(h, precision, grad_x0, (long long)B * LATENT_C * lat_h * lat_w, s, &gpair);
+  if (rc) return rc;
+  auto drop_scratch = [&]() {      // a failed call: its partial parameter gradients must not leak into the next call's sums
+    for (int q = 1; q < dd_handle_s::GRAD_SETS; ++q)
+      for (auto& kv : h->grads[q]) (void)hipMemsetAsync(kv.second->p, 0, kv.second->bytes, s);
+  };
   if (S <= 1) {
     rc = check_finite_begin(h, s); if (rc) return rc;
-    rc = denoise_backward_lane(h, x_T, cond, grad_x0, grad_xT, grad_cond, B, lat_h, lat_w, cond_h, cond_w, T, precision, s, 0, 0, B, ticket, &reused, 1);
+    rc = denoise_backward_lane(h, x_T, cond, grad_x0, grad_xT, grad_cond, B, lat_h, lat_w, cond_h, cond_w, T, precision, s, 0, 0, B, ticket, &reused, 1, gpair);
     if (rc == DD_OK && reused) h->n_traj_reuse++;
-    return rc ? rc : check_finite_report(h, s);
+    if (rc) { if (gpair) drop_scratch(); return rc; }
+    if (gpair) { rc = grad_scale_join(h, 1, s); if (rc) return rc; }
+    return check_finite_report(h, s);
   }
   for (int l = 1; l < S; ++l) {
     if (!h->lane_stream[l]) { rc = acquire_lane_stream(h, l, s); if (rc) return rc; }
@@ -420,24 +477,23 @@ int dd_denoise_backward(dd_handle_t h, const float* x_T, const float* cond, cons
     hipStream_t ls = l == 0 ? s : h->lane_stream[l];
     if (l > 0) DD_HIP(hipStreamWaitEvent(ls, h->lane_fork, 0));
     rc = denoise_backward_lane(h, x_T + img0 * n_x, cond ? cond + img0 * n_c : nullptr, grad_x0 + img0 * n_x, grad_xT ? grad_xT + img0 * n_x : nullptr,
-                               grad_cond ? grad_cond + img0 * n_c : nullptr, n, lat_h, lat_w, cond_h, cond_w, T, precision, ls, l, img0, B, ticket, &reused, S);
+                               grad_cond ? grad_cond + img0 * n_c : nullptr, n, lat_h, lat_w, cond_h, cond_w, T, precision, ls, l, img0, B, ticket, &reused, S, gpair);
     all_reused = all_reused && reused;
     if (l > 0) {
       (void)hipEventRecord(h->lane_done[l], ls);
       (void)hipStreamWaitEvent(s, h->lane_done[l], 0);
     }
     if (rc) {
-      // a failed lane: the partial parameter gradients of the lane sets must not leak into the next call's sums
       h->active_lanes = 1;
-      for (int q = 1; q < dd_handle_s::MAX_LANES; ++q)
-        for (auto& kv : h->grads[q]) (void)hipMemsetAsync(kv.second->p, 0, kv.second->bytes, s);
+      drop_scratch();
       return rc;
     }
     img0 += n;
   }
   h->active_lanes = 1;
-  // after the join, on the caller's stream: set 0 += set l, set l = 0
-  for (int l = 1; l < S; ++l)
+  // after the join, on the caller's stream: set 0 += set l, set l = 0  (a scaled call: x 1/s, its lane 0's set included)
+  if (gpair) { rc = grad_scale_join(h, S, s); if (rc) return rc; }
+  for (int l = 1; l < S && !gpair; ++l)
     for (auto& kv : h->grads[l]) {
       hipError_t e = hipSuccess;
       float* dst = grad_buf(h, kv.first, kv.second->bytes / 4, s, &e, 0); DD_HIP(e);

@@ -689,6 +689,61 @@ hipError_t launch_add_inplace(float* dst, const float* src, long long n, hipStre
   return hipGetLastError();
 }
 
+// ---- power-of-two scale of an incoming gradient that travels as f16 (dd_api_train.cpp: grad_autoscale) ----
+// ws = {fp32 s, fp32 1/s, u32 bits of the largest FINITE |g|}.  The bits of a non-negative float order like the value, so the integer
+// atomicMax gives the same result in any order; NaN / Inf elements take no part (they still travel through the backward as they are).
+__global__ void __launch_bounds__(256) grad_amax_kernel(const float* __restrict__ g, long long n, unsigned* __restrict__ out) {
+  float m = 0.f;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float a = fabsf(g[i]);
+    m = (a <= 3.402823466e+38f && a > m) ? a : m;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) { const float o = __shfl_xor(m, off, 64); m = o > m ? o : m; }
+  if ((threadIdx.x & 63) == 0 && m > 0.f) atomicMax(out, __builtin_bit_cast(unsigned, m));
+}
+// s = 2^(GRAD_AMAX_EXP - floor(log2 amax)): s x amax lies in [2^GRAD_AMAX_EXP, 2^(GRAD_AMAX_EXP + 1)).  Built from the exponent field, so a
+// gradient 2^k times another gets exactly 2^-k times its scale; the shift is held to +-126 (s and 1/s both normal fp32).  amax == 0: s = 1.
+__global__ void grad_scale_pair_kernel(float* __restrict__ ws) {
+  const unsigned bits = reinterpret_cast<const unsigned*>(ws)[2];
+  int shift = 0;
+  if (bits != 0u) {
+    const int e = (bits >> 23) ? (int)(bits >> 23) - 127 : -126;      // (a subnormal fp32 amax: the clamp below decides anyway)
+    shift = GRAD_AMAX_EXP - e;
+    shift = shift > 126 ? 126 : (shift < -126 ? -126 : shift);
+  }
+  ws[0] = __builtin_bit_cast(float, (unsigned)(127 + shift) << 23);
+  ws[1] = __builtin_bit_cast(float, (unsigned)(127 - shift) << 23);
+}
+hipError_t launch_grad_scale(const float* g, long long n, float* ws, hipStream_t s) {
+  hipError_t e = hipMemsetAsync(ws, 0, 3 * sizeof(float), s);
+  if (e != hipSuccess) return e;
+  const long long nb = (n + 256 * 8 - 1) / (256 * 8);
+  hipLaunchKernelGGL(grad_amax_kernel, dim3((unsigned)(nb < 1 ? 1 : (nb > 1024 ? 1024 : nb))), dim3(256), 0, s, g, n, reinterpret_cast<unsigned*>(ws) + 2);
+  hipLaunchKernelGGL(grad_scale_pair_kernel, dim3(1), dim3(1), 0, s, ws);
+  return hipGetLastError();
+}
+// x *= *factor (a power of two read from device memory: exact)
+__global__ void scale_by_kernel(float* __restrict__ x, const float* __restrict__ factor, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) x[i] *= factor[0];
+}
+hipError_t launch_scale_by(float* x, const float* factor, long long n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(scale_by_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, factor, n);
+  return hipGetLastError();
+}
+// dst += *factor x src, src = 0: a call's scaled parameter gradients joined into the accumulated set
+__global__ void add_scaled_clear_kernel(float* __restrict__ dst, float* __restrict__ src, const float* __restrict__ factor, long long n) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n) { dst[i] += factor[0] * src[i]; src[i] = 0.f; }
+}
+hipError_t launch_add_scaled_clear(float* dst, float* src, const float* factor, long long n, hipStream_t s) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(add_scaled_clear_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, dst, src, factor, n);
+  return hipGetLastError();
+}
+
 // dgamma_c += sum_b dgb[b][c][1],  dbeta_c += sum_b dgb[b][c][0]
 __global__ void gn_param_grad_kernel(const double* __restrict__ dgb, float* __restrict__ dgamma, float* __restrict__ dbeta, int B, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;

@@ -244,6 +244,13 @@ hipError_t launch_channel_sum_blocked(const void* v, int ek, float* out, int B, 
 hipError_t launch_upsample_adjoint(const void* g, int ek, float* dst, int B, int C, int ch, int cw, int h, int w, int accumulate, hipStream_t s, bool tiled = true);
 hipError_t launch_channel_sum(const ActView& v, float* out, const long long* rows, int t_base, int t_bstride, int B, hipStream_t s);
 hipError_t launch_add_inplace(float* dst, const float* src, long long n, hipStream_t s);
+// f16 gradients (option "grad_autoscale"): ws = {s, 1/s, scratch} with s the power of two that puts the largest finite |g| into
+// [2^GRAD_AMAX_EXP, 2^(GRAD_AMAX_EXP + 1)) (1 when g is all zero); no host read.  The exponent is the centre of the measured flat region
+// of the f16 backward's error over the gradient's scale (profiles/grad_scale_sweep.json).
+constexpr int GRAD_AMAX_EXP = 2;
+hipError_t launch_grad_scale(const float* g, long long n, float* ws, hipStream_t s);
+hipError_t launch_scale_by(float* x, const float* factor, long long n, hipStream_t s);                              // x *= *factor
+hipError_t launch_add_scaled_clear(float* dst, float* src, const float* factor, long long n, hipStream_t s);     // dst += *factor x src; src = 0
 hipError_t launch_gn_param_grad(const double* dgb, float* dgamma, float* dbeta, int B, int C, hipStream_t s);
 hipError_t launch_naive_wgrad(const ActView& gy, const ActView& a, float* dw_oihw, int B, int h, int w, hipStream_t s);
 // MFMA weight gradient (dd_wgrad.hip), bf16 / f16 operands in the activation layouts, fp32 atomics into dw [CO][CI][3][3]

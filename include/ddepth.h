@@ -228,7 +228,12 @@ int dd_decode(dd_handle_t h, const float* latent, float* depth, int B, int lat_h
  * pred.0 o convB as ONE 5x5 convolution with a per-step border-ring correction, 0 = as two kernels (DD_PREC_F16X3: the reference's order): A/B switch), "layer_timing", "ablate" (timing experiments; honoured in -DDD_ABLATE=1
  * builds only), "naive_wgrad" (1 = backward weight gradients by the unfused kernel
  * instead of the MFMA kernel, A/B check), "x3_grad_fp32" (DD_PREC_F16X3's backward: 0 [default] = f16 gradients through the f16 mode's MFMA kernels
- * behind the split forward, 1 = fp32 gradients through the fp32 mode's kernels, ~60x slower: the parity form), "keep_trajectory" / "use_trajectory" (training: see dd_denoise_backward), "streams" (S > 1:
+ * behind the split forward, 1 = fp32 gradients through the fp32 mode's kernels, ~60x slower: the parity form), "grad_autoscale" (the backward calls whose
+ * gradients travel as f16 -- DD_PREC_F16, and DD_PREC_F16X3 without "x3_grad_fp32": 1 [default] = the incoming gradient (grad_eps / grad_x0, all images of the
+ * call) enters multiplied by a power of two s found on the device from its largest finite magnitude, and grad_x / grad_xT, grad_cond and the call's
+ * parameter gradients leave multiplied by 1/s, so a gradient of any size -- the 1e-7 of a mean over millions of pixels, the 2^16 of a loss scaler -- gets the
+ * arithmetic a unit-sized one gets; no host read, s = 1 for an all-zero gradient, NaN / Inf elements pass through; 0 = the gradient travels as it comes:
+ * below ~1e-3 it sinks into f16's subnormals, beyond 65504 it comes back as NaN), "keep_trajectory" / "use_trajectory" (training: see dd_denoise_backward), "streams" (S > 1:
  * dd_denoise runs the B images as S concurrent sub-batches -- lane 0 on the caller's stream, the others on streams the handle owns, forked
  * and joined by events on the caller's stream, one plan and hipGraph per lane; the images are independent and every image's result is bit-identical to the one-lane call's as long as both take the same tile form -- since round 6 the Res denoiser's hoisted conv3 pair keeps its 8x32 tiles for every lane count (the Swin 5x5 form moves to 16x32 tiles when its 8x32 tiles exceed the resident slots, whatever the lane count), so they do; option "big_tiles" forces one form;
  * dd_denoise_backward splits the same way, with one parameter-gradient set per lane summed into the caller-visible one at the join;

@@ -3,7 +3,9 @@ the C ABI against
   (1) the golden gradients minted by autograd of the reference's own ScheduledCNNRefine (denoise_bwd_res.npz),
   (2) torch autograd of the CPU port on other seeded shapes (ragged sizes, batch > 1, repeated timesteps),
   (3) properties: gradients accumulate across calls and clear with zero_grad; linear in grad_eps; loop backward with
-      T = 1 == one call.
+      T = 1 == one call,
+  (4) the same goldens with the incoming gradient at the scales of a training step (2^-24 .. 2^16 x unit scale; end of the file): same bounds,
+      exact equivariance under a power of two, accumulation, lanes, zero / NaN gradients.
 
 ReLU ties: the gradient is discontinuous where a GroupNorm+ReLU pre-activation is zero, and with ~10^5..10^6 activations per
 call the smallest |pre-activation| is ~1e-6 -- inside the difference between two fp32 implementations, so a max-norm
@@ -40,6 +42,7 @@ SGD_GRAD0_REL = {"res": 0.12, "swin": 0.18}
 SGD_DELTA_REL = {"res": 0.125, "swin": 0.40}
 SGD_COS_MIN = {"res": 0.996, "swin": 0.96}
 PRECS = ["naive_fp32", "fp32", "f16x3", "bf16", "f16"]
+LOOP_TOL = {"naive_fp32": 5e-3, "fp32": 5e-3, "f16x3": 2e-2, "bf16": 3e-1}      # the loop backward (test_loop_backward_matches_reference_autograd_golden)
 
 
 @pytest.fixture(scope="module")
@@ -194,7 +197,7 @@ def test_loop_backward_matches_reference_autograd_golden(U, golden, cases, prec)
     x0 = be.denoise(U.cu(inp["x_T"]), U.cu(inp["cond"]), c["T"], prec).cpu().numpy()
     be.zero_grad()
     gx, gc = be.denoise_backward(U.cu(inp["x_T"]), U.cu(inp["cond"]), U.cu(ge), c["T"], prec, need_grad_xT=True)
-    tol = {"naive_fp32": 5e-3, "fp32": 5e-3, "f16x3": 2e-2, "bf16": 3e-1}[prec]      # (f16x3: relative L2; a ReLU tie flipped over the chained steps shows as ~1e-2 there)
+    tol = LOOP_TOL[prec]      # (f16x3: relative L2; a ReLU tie flipped over the chained steps shows as ~1e-2 there)
     errs = {"x0": _rel(x0, g["x0"], prec), "grad_xT": _rel(gx.cpu().numpy(), g["grad_xT"], prec),
             "grad_cond": _rel(gc.cpu().numpy()[:, :8], g["grad_cond_ch0_8"], prec),
             "grad_cond_sum": _rel(gc.double().sum(dim=(0, 2, 3)).cpu().numpy(), g["grad_cond_chan_sum"], prec)}
@@ -432,13 +435,13 @@ def test_autograd_through_head_modules_matches_torch_port(U, cases):
     assert not bad, bad
 
 
-@pytest.mark.parametrize("prec", ["fp32", "f16x3"])
-def test_head_training_step_matches_reference_golden(U, golden, cases, prec):
+def _head_training_step(U, golden, cases, prec, loss_scale=1.0):
     """One training-mode step of the drop-in head (BatchNorm on batch statistics in the PyTorch-ROCm FPN / codec, the DDIM
     loop and ddim_loss through the HIP forward AND backward, RNG draws injected) against the same step of the reference head
     run under autograd on CPU (head_train_res.npz): loss, prediction, gradients w.r.t. the backbone features and a sample of
     parameter gradients from every part of the head.  Tolerance 1e-2 of max per tensor (ReLU ties, see module docstring;
-    MIOpen vs oneDNN convolutions in the torch-side FPN / codec), loss 1e-4."""
+    MIOpen vs oneDNN convolutions in the torch-side FPN / codec), loss 1e-4.
+    loss_scale: the loss is multiplied by it in front of backward() and every gradient divided by it afterwards (a power of two: exact)."""
     import diffusiondepth_amd as dda
     c, g = cases["head_train_res"], golden("head_train_res")
     sd = synth.make_state_dict(c["wseed"], "res", c["decoder_gain"], c["decoder_log_scale"])
@@ -462,23 +465,35 @@ def test_head_training_step_matches_reference_golden(U, golden, cases, prec):
     try:
         out = head(fp, gt, gt > 0, gt_depth_map=gt, return_loss=False)
         loss = (out["pred"] - gt).abs().mean() + out["ddim_loss"]
-        loss.backward()
+        (loss * loss_scale).backward()
     finally:
         torch.randn, torch.randint = real_randn, real_randint
         torch.backends.cudnn.allow_tf32 = prev
     lv = float(loss.detach())
     assert abs(lv - float(g["loss"][0])) <= 1e-4 * abs(float(g["loss"][0]))
+    unscaled = lambda t: t.cpu().numpy().astype(np.float64) / loss_scale
     errs = {"pred": _rel(out["pred"].detach().cpu().numpy(), g["pred"]),
-            "grad_fp3": _rel(fp[3].grad.cpu().numpy(), g["grad_fp3"]), "grad_fp0": _rel(fp[0].grad.cpu().numpy()[:, :4], g["grad_fp0_ch0_4"])}
+            "grad_fp3": _rel(unscaled(fp[3].grad), g["grad_fp3"]), "grad_fp0": _rel(unscaled(fp[0].grad)[:, :4], g["grad_fp0_ch0_4"])}
     named = dict(head.named_parameters())
     for k in c["grad_keys"]:
-        got = named[k].grad.cpu().numpy()
+        got = unscaled(named[k].grad)
         if got.size > 5000:
             got = got.reshape(-1)[::c["grad_stride"]]
         errs[k] = _rel(got, g["grad." + k])
-    U.record("head_train", prec=prec, loss=lv, **errs)
-    bad = {k: v for k, v in errs.items() if v > 1e-2}
+    U.record("head_train", prec=prec, loss=lv, loss_scale=loss_scale, **errs)
+    bad = {k: v for k, v in errs.items() if not v <= 1e-2}
     assert not bad, bad
+
+
+@pytest.mark.parametrize("prec", ["fp32", "f16x3"])
+def test_head_training_step_matches_reference_golden(U, golden, cases, prec):
+    _head_training_step(U, golden, cases, prec)
+
+
+def test_head_training_step_with_the_loss_scaled_down_matches_reference_golden(U, golden, cases):
+    """The same step in f16x3 with loss x 2^-16 in front of backward() and the gradients x 2^16 behind it: the gradients that reach the library are
+    2^-16 of already small ones (means over pixels), far below f16's normal range -- the same golden, the same 1e-2."""
+    _head_training_step(U, golden, cases, "f16x3", loss_scale=2.0 ** -16)
 
 
 def _golden_param_errs(be, g, prec):
@@ -546,3 +561,226 @@ def test_swin_loop_backward_matches_torch_port_autograd(U, cases):
         U.record("loop_bwd_swin", kept=keep, **{k.replace("model.", ""): v for k, v in errs.items()})
         bad = {k: v for k, v in errs.items() if v > 5e-3}       # ReLU-tie sensitivity over chained steps, see the Res loop test
         assert not bad, (keep, bad)
+
+
+# ---- incoming gradients at the scale of a training step -----------------------------------------------------------------------------------------------
+# Everything above feeds the library a unit-scale gradient.  A training step's is the gradient of a MEAN over millions of latent elements
+# (ddim_loss = mse_loss: |grad_eps| ~ 2 / numel ~ 2^-22 at KITTI size, B = 4), a loss scaler's is 2^16 times larger.  The backward is linear in
+# that gradient, so the k = 0 golden is the reference at every scale: the calls below run on 2^k x grad_eps, the results are divided by 2^k in fp64
+# and held to the SAME bounds.  The f16-gradient modes ("f16", "f16x3") pass because the library rescales the gradient by a power of two on its way
+# in (option "grad_autoscale"); without it they lose the gradient to f16's subnormals (k <= -14) or to its range (k = +16).
+SCALE_KS = [-24, -20, -14, 16]
+SCALE_PRECS = ["fp32", "bf16", "f16", "f16x3"]
+_shared = {}      # references and k = 0 results, computed once per (case, precision)
+
+
+def _once_case(U, cases, golden, variant):
+    """(backend, golden, (x, t, cond) on the GPU, grad_eps on the host) of the golden backward case of a variant"""
+    name = "denoise_bwd_swin" if variant == "swin" else "denoise_bwd_res"
+    if name not in _shared:
+        c = cases[name]
+        inp = synth.make_inputs(c["iseed"], c["B"], c["h"], c["w"], tuple(c["cond_hw"]) if variant == "swin" else None)
+        ge = np.random.RandomState(c["gseed"]).standard_normal(inp["x_T"].shape).astype(np.float32)
+        _shared[name] = (inp, ge)
+    inp, ge = _shared[name]
+    return U.backend_for(cases[name]), golden(name), (U.cu(inp["x_T"]), U.cu(inp["timesteps"]), U.cu(inp["cond"])), ge, inp
+
+
+def _scaled(ge, k):
+    return (ge * np.float32(2.0 ** k)).astype(np.float32)      # a power of two: exact
+
+
+def _once_errs(be, g, gx, gc, prec, sc):
+    """errors of one call's results, divided by sc in fp64, against a golden file (as test_swin_backward_matches_reference_autograd_golden)"""
+    un = lambda a: a.astype(np.float64) / sc
+    errs = {"grad_x": _rel(un(gx.cpu().numpy()), g["grad_x"], prec), "grad_cond": _rel(un(gc.cpu().numpy()[:, :8]), g["grad_cond_ch0_8"], prec),
+            "grad_cond_sum": _rel(un(gc.double().sum(dim=(0, 2, 3)).cpu().numpy()), g["grad_cond_chan_sum"], prec)}
+
+    class Unscaled:      # be.grad(...) / sc in fp64, for _golden_param_errs
+        def grad(self, name):
+            return be.grad(name).double() / sc
+    errs.update(_golden_param_errs(Unscaled(), g, prec))
+    return {k: (v if np.isfinite(v) else float("inf")) for k, v in errs.items()}
+
+
+@pytest.mark.parametrize("k", SCALE_KS)
+@pytest.mark.parametrize("prec", SCALE_PRECS)
+@pytest.mark.parametrize("variant", ["res", "swin"])
+def test_backward_at_gradient_scale_matches_reference_autograd_golden(U, golden, cases, variant, prec, k):
+    """dd_denoise_once_backward on 2^k x grad_eps, results / 2^k, against the reference's autograd golden at the file's own TOL[prec]."""
+    be, g, args, ge, _ = _once_case(U, cases, golden, variant)
+    be.zero_grad()
+    gx, gc = be.denoise_once_backward(*args, U.cu(_scaled(ge, k)), prec)
+    errs = _once_errs(be, g, gx, gc, prec, 2.0 ** k)
+    U.record("bwd_golden_scaled", variant=variant, prec=prec, k=k, **{n.replace("model.", ""): v for n, v in errs.items()})
+    print(variant, prec, k, errs)
+    bad = {n: v for n, v in errs.items() if not v <= TOL[prec]}
+    assert not bad, bad
+
+
+def test_without_the_rescale_small_f16_gradients_miss_the_bound(U, golden, cases):
+    """Option "grad_autoscale" = 0 is the arithmetic without the rescale: f16x3 at k = -20 then misses its 5e-3 (the gradient sits in f16's
+    subnormals: quantum 6e-8 against values of 1e-6) -- so the option does switch something and the tests above do see it."""
+    be, g, args, ge, _ = _once_case(U, cases, golden, "res")
+    be.set_option("grad_autoscale", 0)
+    try:
+        be.zero_grad()
+        gx, gc = be.denoise_once_backward(*args, U.cu(_scaled(ge, -20)), "f16x3")
+        errs = _once_errs(be, g, gx, gc, "f16x3", 2.0 ** -20)
+    finally:
+        be.set_option("grad_autoscale", 1)
+    U.record("bwd_golden_scaled_autoscale_off", prec="f16x3", k=-20, **{n.replace("model.", ""): v for n, v in errs.items()})
+    assert max(errs.values()) > TOL["f16x3"], errs
+
+
+def _loop_ref(cases, variant):
+    """torch autograd of the CPU port through the T = 2 loop on the golden backward case's inputs, once per variant"""
+    from oracle import torch_cpu_port as P
+    key = ("loop_ref", variant)
+    if key not in _shared:
+        c = cases["denoise_bwd_swin" if variant == "swin" else "denoise_bwd_res"]
+        inp = synth.make_inputs(c["iseed"], c["B"], c["h"], c["w"], tuple(c["cond_hw"]) if variant == "swin" else None)
+        ge = np.random.RandomState(6).standard_normal(inp["x_T"].shape).astype(np.float32)
+        sd = P.to_torch_sd(synth.make_state_dict(c["wseed"], variant))
+        _, rgx, rgc, rgrads = P.ddim_loop_vjp(sd, inp["x_T"], inp["cond"], ge, T=2, variant=variant)
+        _shared[key] = (inp, ge, rgx.numpy(), rgc.numpy(), {n: v.numpy() for n, v in rgrads.items()})
+    return _shared[key]
+
+
+@pytest.mark.parametrize("k", SCALE_KS)
+@pytest.mark.parametrize("prec", ["fp32", "bf16", "f16x3"])
+@pytest.mark.parametrize("variant", ["res", "swin"])
+def test_loop_backward_at_gradient_scale_matches_torch_port_autograd(U, cases, variant, prec, k):
+    """dd_denoise_backward (T = 2) on 2^k x grad_x0, results / 2^k, against torch autograd of the CPU port at the loop backward's bounds (LOOP_TOL:
+    the precisions the file has a loop bound for; the f16 mode's loop is held by the exact-equivariance test below).  One scale per call: grad_cond
+    accumulates over the steps at that scale."""
+    inp, ge, rgx, rgc, rgrads = _loop_ref(cases, variant)
+    be = U.backend_for(cases["denoise_bwd_swin" if variant == "swin" else "denoise_bwd_res"])
+    sc = 2.0 ** k
+    be.zero_grad()
+    gx, gc = be.denoise_backward(U.cu(inp["x_T"]), U.cu(inp["cond"]), U.cu(_scaled(ge, k)), 2, prec, need_grad_xT=True)
+    un = lambda t: t.cpu().numpy().astype(np.float64) / sc
+    errs = {"grad_xT": _rel(un(gx), rgx, prec), "grad_cond": _rel(un(gc), rgc, prec)}
+    for name, ref in rgrads.items():
+        errs[name] = _rel(un(be.grad(name)), ref, prec)
+    errs = {n: (v if np.isfinite(v) else float("inf")) for n, v in errs.items()}
+    U.record("loop_bwd_port_scaled", variant=variant, prec=prec, k=k, **{n.replace("model.", ""): v for n, v in errs.items()})
+    print(variant, prec, k, errs)
+    bad = {n: v for n, v in errs.items() if not v <= LOOP_TOL[prec]}
+    assert not bad, bad
+
+
+def _run_at_scale(U, cases, golden, what, prec, k):
+    """[grad_x, grad_cond] (GPU tensors) and {name: parameter gradient} of the single call ("res" / "swin") or the T = 2 loop ("loop") on 2^k x g"""
+    if what == "loop":
+        inp, ge, *_ = _loop_ref(cases, "res")
+        be = U.backend_for(cases["denoise_bwd_res"])
+        be.zero_grad()
+        out = be.denoise_backward(U.cu(inp["x_T"]), U.cu(inp["cond"]), U.cu(_scaled(ge, k)), 2, prec, need_grad_xT=True)
+    else:
+        be, _, args, ge, _ = _once_case(U, cases, golden, what)
+        be.zero_grad()
+        out = be.denoise_once_backward(*args, U.cu(_scaled(ge, k)), prec)
+    return list(out), {n: be.grad(n) for n in be.param_shapes()}
+
+
+@pytest.mark.parametrize("k", SCALE_KS)
+@pytest.mark.parametrize("prec", SCALE_PRECS)
+@pytest.mark.parametrize("what", ["res", "swin", "loop"])
+def test_backward_is_exactly_equivariant_under_a_power_of_two(U, golden, cases, what, prec, k):
+    """grad_x / grad_xT and grad_cond of the call on 2^k x g equal 2^k x those of the call on g BIT FOR BIT, in every precision: fp32 and bf16
+    because a power of two commutes with every operation of theirs (and they must stay that way), f16 / f16x3 because the library's scale is an
+    exact power of two taken from the exponent of the largest magnitude -- both calls then run on the same scaled values.  The parameter gradients
+    (atomics: another summation order per run) within 2e-5 of max, the file's bound for that (test_mfma_wgrad_equals_unfused_wgrad)."""
+    key = ("k0", what, prec)
+    if key not in _shared:
+        _shared[key] = _run_at_scale(U, cases, golden, what, prec, 0)
+    base, base_p = _shared[key]
+    got, got_p = _run_at_scale(U, cases, golden, what, prec, k)
+    sc = 2.0 ** k
+    for name, a, b in zip(("grad_x", "grad_cond"), got, base):
+        assert torch.isfinite(a).all(), name
+        assert torch.equal(a, b * sc), (name, float((a.double() / sc - b.double()).abs().max()), float(b.abs().max()))
+    bad = {n: _rel(got_p[n].double().cpu().numpy() / sc, base_p[n].cpu().numpy()) for n in base_p}
+    bad = {n: e for n, e in bad.items() if not e <= 2e-5}
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("prec", ["f16x3", "f16"])
+def test_scaled_calls_accumulate_unscaled_gradients_and_clear(U, golden, cases, prec):
+    """After zero_grad, a call on g and a call on 2^-20 g leave (1 + 2^-20) x the gradients of the one call (2e-5 of max): what a call's scaled
+    arithmetic produces never stays in the accumulated set.  zero_grad clears everything, and the call after it gives the one call's gradients again
+    (nothing left over in the scratch sets)."""
+    be, _, args, ge, _ = _once_case(U, cases, golden, "res")
+    names = list(be.param_shapes())
+    be.zero_grad()
+    be.denoise_once_backward(*args, U.cu(ge), prec)
+    one = {n: be.grad(n).cpu().numpy() for n in names}
+    be.zero_grad()
+    be.denoise_once_backward(*args, U.cu(ge), prec)
+    be.denoise_once_backward(*args, U.cu(_scaled(ge, -20)), prec)
+    two = {n: be.grad(n).cpu().numpy() for n in names}
+    bad = {n: _rel(two[n], (1.0 + 2.0 ** -20) * one[n].astype(np.float64)) for n in names}
+    assert not {n: e for n, e in bad.items() if not e <= 2e-5}, bad
+    be.zero_grad()
+    assert all(float(be.grad(n).abs().max()) == 0.0 for n in names)
+    be.denoise_once_backward(*args, U.cu(_scaled(ge, -20)), prec)
+    bad = {n: _rel(be.grad(n).double().cpu().numpy() * 2.0 ** 20, one[n]) for n in names}
+    assert not {n: e for n, e in bad.items() if not e <= 2e-5}, bad
+
+
+def test_small_gradients_as_concurrent_lanes_equal_one_stream(U):
+    """test_training_pair_as_concurrent_lanes_equals_one_stream in f16x3 with g x 2^-20, three images on two lanes: the scale is ONE per call, found over
+    the whole batch in front of the fork, so the per-image results do not depend on which images share a lane."""
+    import diffusiondepth_amd as dda
+    be = dda.HipDenoiser(variant="res")
+    be.load_state_dict(synth.make_state_dict(7240, "res"))
+    be.set_schedule(dda.DDIMScheduler().alphas_cumprod)
+    B, h, w, T = 3, 24, 72, 3
+    inp = synth.make_inputs(31, B, h, w)
+    x, cond = U.cu(inp["x_T"]), U.cu(inp["cond"])
+    g = np.random.RandomState(2).standard_normal(inp["x_T"].shape).astype(np.float32)
+    g[1:] *= 2.0 ** -7                            # the images' gradients differ in size: a per-lane scale would differ between the lanes
+    g = U.cu(_scaled(g, -20))
+    names = list(be.param_shapes())
+    res = {}
+    try:
+        for S in (1, 2):
+            be.set_option("streams", S)
+            n0 = be.counter("lane_calls")
+            out = be.denoise(x, cond, T, "f16x3", keep_trajectory=True)
+            be.zero_grad()
+            gx, gc = be.denoise_backward(x, cond, g, T, "f16x3", need_grad_xT=True, trajectory_ticket=be.last_trajectory_ticket)
+            assert be.counter("lane_calls") == n0 + (2 if S > 1 else 0)
+            res[S] = [out, gx, gc] + [be.grad(n) for n in names]
+    finally:
+        be.set_option("streams", 1)
+    for i in range(3):
+        assert torch.equal(res[2][i], res[1][i]), ("x0", "grad_xT", "grad_cond")[i]
+    assert float(res[1][1].abs().max()) > 0.0
+    bad = {n: _rel(a.cpu().numpy(), b.cpu().numpy()) for n, a, b in zip(names, res[2][3:], res[1][3:])}
+    assert not {n: e for n, e in bad.items() if not e <= 2e-5}, bad
+    be.close()
+
+
+@pytest.mark.parametrize("prec", ["f16x3", "f16"])
+def test_zero_and_nan_gradients_in_the_f16_gradient_modes(U, golden, cases, prec):
+    """grad_eps == 0: every gradient exactly zero and finite (a largest magnitude of 0 must not turn into an infinite scale), single call and loop.
+    One NaN in grad_eps: grad_x is not finite -- the head's FloatingPointError guard keeps seeing a poisoned step."""
+    be, _, args, ge, inp = _once_case(U, cases, golden, "res")
+    names = list(be.param_shapes())
+    zero = U.cu(np.zeros_like(ge))
+    for loop in (False, True):
+        be.zero_grad()
+        if loop:
+            gx, gc = be.denoise_backward(args[0], args[2], zero, 2, prec, need_grad_xT=True)
+        else:
+            gx, gc = be.denoise_once_backward(*args, zero, prec)
+        for name, a in [("grad_x", gx), ("grad_cond", gc)] + [(n, be.grad(n)) for n in names]:
+            assert torch.isfinite(a).all() and float(a.abs().max()) == 0.0, (loop, name)
+    poisoned = ge.copy()
+    poisoned[0, 3, 2, 5] = np.nan
+    be.zero_grad()
+    gx, _ = be.denoise_once_backward(*args, U.cu(_scaled(poisoned, -20)), prec)
+    assert not torch.isfinite(gx).all()
+    be.zero_grad()

@@ -638,19 +638,25 @@ def test_backward_vs_reference_autograd_golden(lib, golden, cases, prec):
     if prec == "f16x3":
         # the default form: f16 gradients through the f16 mode's MFMA kernels behind the SAME forward (exact ReLU masks and statistics): relative L2
         rel = lambda a, b: float(np.sqrt(((np.asarray(a, np.float64) - b) ** 2).sum()) / np.sqrt((np.asarray(b, np.float64) ** 2).sum()))
-        be.ck(lib.dd_zero_grad(be.h, None), "dd_zero_grad")
-        gx[:], gc[:] = np.nan, np.nan
-        be.ck(lib.dd_denoise_once_backward(be.h, _p(x), _p(t), _p(cond), _p(ge), _p(gx), _p(gc), B, h, w, h, w, dda.backend.precision_id(prec), None),
-              "dd_denoise_once_backward")
-        errs = {"grad_x": rel(gx, g["grad_x"]), "grad_cond": rel(gc[:, :8], g["grad_cond_ch0_8"])}
-        for name in names:
-            key = "grad." + name
-            if key in g:
-                out = np.full(g[key].shape, np.nan, np.float32)
-                be.ck(lib.dd_get_grad(be.h, name.encode(), _p(out), out.size, None), "dd_get_grad")
-                errs[name] = rel(out, g[key])
-        print("f16x3 backward, f16 gradients: relative L2", errs)
-        assert max(errs.values()) < X3_F16_GRAD_REL, errs
+        # ... at unit scale and at the scales a training step meets (k = -20: the gradient of a mean over millions of elements; k = +16: under a loss
+        # scaler): the call on 2^k x grad_eps, results / 2^k in fp64, against the same golden (linear in grad_eps) at the same bound -- the library
+        # rescales an f16 gradient by a power of two on its way in (option "grad_autoscale")
+        for k in (0, -20, 16):
+            sc = 2.0 ** k
+            gek = (ge * np.float32(sc)).astype(np.float32)
+            be.ck(lib.dd_zero_grad(be.h, None), "dd_zero_grad")
+            gx[:], gc[:] = np.nan, np.nan
+            be.ck(lib.dd_denoise_once_backward(be.h, _p(x), _p(t), _p(cond), _p(gek), _p(gx), _p(gc), B, h, w, h, w, dda.backend.precision_id(prec), None),
+                  "dd_denoise_once_backward")
+            errs = {"grad_x": rel(gx.astype(np.float64) / sc, g["grad_x"]), "grad_cond": rel(gc[:, :8].astype(np.float64) / sc, g["grad_cond_ch0_8"])}
+            for name in names:
+                key = "grad." + name
+                if key in g:
+                    out = np.full(g[key].shape, np.nan, np.float32)
+                    be.ck(lib.dd_get_grad(be.h, name.encode(), _p(out), out.size, None), "dd_get_grad")
+                    errs[name] = rel(out.astype(np.float64) / sc, g[key])
+            print("f16x3 backward, f16 gradients x 2^%d: relative L2" % k, errs)
+            assert all(v < X3_F16_GRAD_REL for v in errs.values()), (k, errs)      # (a NaN fails this too)
 
 
 # ---- multi-scale deformable attention of the HAHI neck (include/ddepth_msda.h) --------------------------------------------------------------------
