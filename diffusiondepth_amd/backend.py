@@ -204,10 +204,11 @@ class HipDenoiser:
         'depth_head.').  Keys the library does not own (backbone, convup_fp, num_batches_tracked) are ignored.  ``sd`` may hold any
         subset of the three parameter groups (model.* / depth_transform.* / conv_lateral.* + conv_up.*); each group must be complete.
 
-        device_route: denoiser parameters (model.*) that are tensors on this device go to the library without leaving HBM
-        (dd_set_weight_device: fp32 -> kernel layouts by pack kernels) instead of D2H copy + host-side packing -- what a training loop
-        needs after every optimizer.step().  None = the environment variable DDEPTH_DEVICE_WEIGHTS (default "1": the route leaves the host
-        packer's bytes in HBM, digest-equal -- host emulation and, since round 2, tests/test_zzz_gpu_device_weights.py on an MI355X)."""
+        device_route: denoiser parameters (model.*) that are tensors on this device are handed over as device pointers
+        (dd_set_weight_device) and never leave HBM -- what a training loop needs after every optimizer.step(); otherwise, and for every
+        other group, the values travel as host arrays (dd_set_weight) and the library uploads them at commit.  Either way the same pack
+        kernels write the same weight images (tests/test_zzz_gpu_device_weights.py).  None = the environment variable
+        DDEPTH_DEVICE_WEIGHTS (default "1")."""
         torch = _torch()
         if device_route is None:
             device_route = os.environ.get("DDEPTH_DEVICE_WEIGHTS", "1") == "1"
@@ -249,7 +250,7 @@ class HipDenoiser:
         return n
 
     def weights_digest(self) -> int:
-        """Test hook (dd_debug_weights_digest): digest of every packed denoiser weight buffer in HBM."""
+        """Test hook (dd_debug_weights_digest): digest of every packed denoiser weight buffer in HBM, and of the FPN's and neck's once loaded."""
         d = ctypes.c_uint64()
         with _torch().cuda.device(self.device):
             self._ck(self._lib.dd_debug_weights_digest(self._h, ctypes.byref(d)), "dd_debug_weights_digest")

@@ -784,7 +784,8 @@ int dd_debug_fetch(dd_handle_t h, const char* name, float* out, int64_t numel, v
 }
 
 // FNV-1a over every packed / staged denoiser weight buffer as it sits in HBM (buffer sizes included): two handles fed the same
-// parameters through different routes (dd_set_weight vs dd_set_weight_device) must agree.
+// parameters through different calls (dd_set_weight vs dd_set_weight_device) must agree, and with the digests recorded from the former
+// host-side packer (tests/golden/weight_digests.json).
 int dd_debug_weights_digest(dd_handle_t h, uint64_t* digest) {
   if (!h || !digest) return DD_ERR_INVALID_ARG;
   if (!h->committed) return h->fail(DD_ERR_STATE, "dd_debug_weights_digest: model.* weights not committed");
@@ -817,6 +818,22 @@ int dd_debug_weights_digest(dd_handle_t h, uint64_t* digest) {
   if (h->variant == DD_VARIANT_SWIN) { DD_HIP(eat_layer(h->LA)); DD_HIP(eat_layer(h->LB)); }
   DD_HIP(eat(h->emb));
   DD_HIP(eat(h->etab));
+  // the folded condition FPN and HAHI neck, once committed (a handle that holds the denoiser group alone digests as it always has)
+  if (h->fpn_committed) {
+    for (int i = 0; i < FPN_LEVELS; ++i) {
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_HIP(eat(h->fpn_lat_w[i][wi]));
+      DD_HIP(eat(h->fpn_lat_b[i]));
+    }
+    for (int j = 0; j < FPN_LEVELS - 1; ++j) {
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_HIP(eat(h->fpn_up_w[j][wi]));
+      DD_HIP(eat(h->fpn_up_b[j]));
+    }
+  }
+  if (h->neck_committed)
+    for (int c = 0; c < NECK_CONVS; ++c) {
+      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_HIP(eat(h->neck_w[c][wi]));
+      DD_HIP(eat(h->neck_b[c]));
+    }
   *digest = d;
   return DD_OK;
 }

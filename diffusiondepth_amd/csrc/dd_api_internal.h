@@ -2,7 +2,7 @@
 // functions one unit defines and another calls.  Round 5 split the 2 500-line dd_api.cpp by concern, no behaviour change:
 //   dd_api.cpp          handle lifetime, schedule, options, counters, dd_condition / dd_neck_condition, dd_denoise / _trace / _once (lanes), q_sample,
 //                       latent codec, debug fetches
-//   dd_api_weights.cpp  parameter intake (dd_set_weight / _device), packing into the kernels' weight images, dd_commit_weights
+//   dd_api_weights.cpp  parameter intake (dd_set_weight / _device), dd_commit_weights: BatchNorm folds on the host, every weight image by the pack kernel of dd_misc.hip
 //   dd_api_plans.cpp    per-shape plans (buffers, schedule tables, hoisted terms), the launch sequence of one denoiser call / one loop body, graphs' inputs
 //   dd_api_train.cpp    gradients: dd_denoise_once_backward, dd_denoise_backward (lanes), dd_zero_grad / dd_get_grad
 #pragma once
@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <list>
 #include <map>
 #include <memory>
 #include <set>
@@ -44,24 +45,12 @@ struct DevBuf {
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-inline uint16_t host_f32_to_bf16(float f) {
-  uint32_t u;
-  std::memcpy(&u, &f, 4);
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (uint16_t)(u >> 16);
-}
-inline uint16_t host_f32_to_f16(float f) {
-  _Float16 hf = (_Float16)f;       // round-to-nearest-even
-  uint16_t u;
-  std::memcpy(&u, &hf, 2);
-  return u;
-}
-
 constexpr int NUM_EK = 3;     // weight images every convolution has: fp32, bf16, f16 (index = element kind)
 constexpr int NUM_WIMG = 5;   // ... the denoiser's forward convolutions have a fourth: the split-f16 image of the mode EK_F16S (index WIMG_SPLIT),
 constexpr int WIMG_SPLIT = 3; // and conv4 a fifth: the f16 image with the weights' lo halves stacked into its padding cout rows (EK_F16R, index WIMG_STACK)
 constexpr int WIMG_STACK = 4;
 inline int wimg_kind(int slot) { return slot == WIMG_SPLIT ? (int)EK_F16S : slot == WIMG_STACK ? (int)EK_F16R : slot; }     // image slot -> kind handed to the packers / conv_pack_geom2
+constexpr int kImageSlots[4] = {EK_F32, EK_BF16, EK_F16, WIMG_SPLIT};     // the images of a folded FPN / neck convolution and of the hoisted 5x5 form; the first NUM_EK: the plain kinds
 inline int wimg_slot(int kind) { return kind == EK_F16S ? WIMG_SPLIT : kind; }
 inline bool wimg_has(int slot, int fwd_layer) { return slot != WIMG_STACK || fwd_layer == KID_CONV4; }     // which convolution carries which image
 // precision -> element kind / mode of the fused kernels.  DD_PREC_BF16 is the mode EK_BF16M (bf16 operands on the large convolutions, f16
@@ -204,8 +193,9 @@ struct dd_handle_s {
   int variant = DD_VARIANT_RES;
   std::string err;
   std::map<std::string, std::vector<float>> host_w;
-  std::map<std::string, std::unique_ptr<DevBuf>> dev_w;   // dd_set_weight_device: fp32 device copies (denoiser group)
-  std::set<std::string> dev_newer;                        // names whose device copy is newer than host_w's (or that have no host copy)
+  std::map<std::string, std::unique_ptr<DevBuf>> dev_w;   // denoiser group: fp32 device copies, what dd_commit_weights packs from (dd_set_weight_device, or uploaded from host_w at commit)
+  std::set<std::string> dev_newer;                        // names whose device copy holds the newest value (a dd_set_weight of the name takes it out again)
+  DevBuf stage;                                           // dd_commit_weights: one folded fp32 tensor of the FPN / neck on its way into the pack kernel (released at the end of the call)
   bool committed = false;      // denoiser group (model.*) packed
   bool codec_committed = false; // codec group (depth_transform.*) packed
   ConvLayer L[4];
@@ -252,7 +242,7 @@ struct dd_handle_s {
   int f16r_c1 = 1;            // DD_PREC_F16R: conv1's weights as an f16 pair (two MFMAs; 0 = the plain f16 kernel)
   int f16r_p4 = 0;            // DD_PREC_F16R: conv4's operand as an f16 pair as well (two MFMAs per tap)
   bool split_ok = true;       // every forward convolution weight fits the split-f16 images (|w| x 256 inside f16): DD_PREC_F16X3 / DD_PREC_F16R refuse to run otherwise
-  DevBuf wmax;                // device route: bits of max |w| over the forward convolution weights (launch_max_abs)
+  DevBuf wmax;                // dd_commit_weights: bits of max |w| over the packed tensors of the denoiser / FPN / neck group (launch_max_abs), one word each
   int resident_slots = 512;   // workgroup slots the chip holds at two per CU (dd_create: 2 x multiProcessorCount): the big-tile rule and thin_slots' default
   hipStream_t lane_stream[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
   std::vector<hipEvent_t> probe_events;
@@ -330,13 +320,10 @@ constexpr int kCins[4] = {LATENT_C, HID_C, COND_C, HID_C}, kCouts[4] = {HID_C, C
 // dd_api_weights.cpp
 int weight_group(const std::string& name);
 std::vector<WeightSpec> required_weights(int variant, int pyr = PYR_DEFAULT);
-bool pack_conv_weights(const float* w_oihw, const PackGeom& g, int ek, bool swizzle, std::vector<uint8_t>& out);
 int pack_geom(dd_handle_t h, int kid, int ek, PackGeom* g);      // conv_pack_geom2, failing the call for a pair no kernel runs
-int upload(dd_handle_t h, DevBuf& dst, const void* src, size_t bytes, hipStream_t s);
-int pull_device_weights_to_host(dd_handle_t h, hipStream_t s);
-int ensure_bytes(dd_handle_t h, DevBuf& dst, size_t bytes);
-int pack_conv_layer_device(dd_handle_t h, ConvLayer& L, const float* w, int fwd_layer, int dgrad_layer, bool with_naive, hipStream_t s);
-int commit_model_from_device(dd_handle_t h, hipStream_t s);
+int device_buf(dd_handle_t h, DevBuf& dst, size_t bytes, const void* src = nullptr, hipStream_t s = nullptr);      // dst holds >= bytes; src: filled from that host array on s
+// device fp32 W[cout][cin][ks][ks] -> images[slots[i]] of kernel `kid` (pack_weights_kernel); numel must be the element count of the kernel's geometry
+int pack_images(dd_handle_t h, const float* w, int64_t numel, int kid, const int* slots, int n_slots, DevBuf* images, bool transposed, hipStream_t s);
 // dd_api_plans.cpp
 int check_common(dd_handle_t h, int B, int lh, int lw, int ch, int cw, bool need_schedule);
 int lane_count(dd_handle_t h, int B, int precision);

@@ -421,14 +421,7 @@ int ensure_swin_w5(dd_handle_t h, hipStream_t s) {
     DD_HIP(h->w5_oihw.alloc((size_t)HID_C * COND_C * 25 * 4)); DD_HIP(h->pairp.alloc((size_t)81 * COND_C * HID_C * 4)); DD_HIP(h->kside.alloc(SWIN_KSIDE_BYTES));
   }
   DD_HIP(launch_swin_compose(h->LB.w_oihw.as<float>(), h->L[2].w_oihw.as<float>(), h->w5_oihw.as<float>(), h->pairp.as<float>(), h->kside.p, s));
-  for (int wi = 0; wi < NUM_WIMG; ++wi) {
-    if (wi == WIMG_STACK) continue;
-    const int ekk = wimg_kind(wi);
-    PackGeom g5;
-    int rc = pack_geom(h, SWIN_PRED5_H, ekk, &g5); if (rc) return rc;
-    rc = ensure_bytes(h, h->w5pack[wi], pack_weights_bytes(g5, ekk)); if (rc) return rc;
-    DD_HIP(launch_pack_weights(h->w5_oihw.as<float>(), h->w5pack[wi].p, g5, ekk, true, false, s));
-  }
+  DD_TRY(pack_images(h, h->w5_oihw.as<float>(), (int64_t)HID_C * COND_C * 25, SWIN_PRED5_H, kImageSlots, 4, h->w5pack, false, s));
   h->w5_weights = h->weights_serial;
   return DD_OK;
 }

@@ -118,7 +118,7 @@ int bwd_core(dd_handle_t h, Plan* pl, const float* x_nhwc, const long long* tv, 
       h->chk_labels.push_back(std::string(what) + " of layer " + std::to_string(l) + " (step slot " + std::to_string(sstep) + ", lane " + std::to_string(lane) + ")");
       return DD_OK;
     }
-    // (mode 1 counts into the LAST entry of the option's own buffer: h->wmax is the weight-range scratch of the device weight route)
+    // (mode 1 counts into the LAST entry of the option's own buffer: h->wmax is the weight-range scratch of dd_commit_weights)
     if (!h->chk_buf.p) DD_HIP(h->chk_buf.alloc(16384 * sizeof(unsigned)));
     unsigned* cnt = h->chk_buf.as<unsigned>() + 16383;
     DD_HIP(hipMemsetAsync(cnt, 0, sizeof(unsigned), s));

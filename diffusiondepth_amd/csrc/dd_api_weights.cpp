@@ -67,65 +67,6 @@ std::vector<WeightSpec> required_weights(int variant, int pyr) {
   return v;
 }
 
-// Packed layout consumed by conv_igemm_kernel:
-//   [n_tile][cin_chunk][tap_group][tap_in_group][n (NT)][k (CK)]  of  W[cout][cin][dy][dx]   (zero beyond COUT; ks x ks taps)
-// returns false when a weight does not fit the split-f16 image (|w| x SPLIT_WSCALE beyond f16): dd_commit_weights records it in
-// dd_handle_s::split_ok and the split modes (DD_PREC_F16X3 / DD_PREC_F16R) refuse to run on such parameters -- the other precisions are unaffected
-bool pack_conv_weights(const float* w_oihw, const PackGeom& g, int ek, bool swizzle, std::vector<uint8_t>& out) {
-  bool fits = true;
-  const int ks = g.ks, n_tiles = g.cout_pad / g.nt, n_chunks = g.cin / g.ck, n_tg = ks * ks / g.tg;
-  const int planes = g.planes > 1 ? 2 : 1;       // split f16 (EK_F16S): every stage block is [hi plane | lo plane] of f16 elements
-  const size_t n_el = (size_t)n_tiles * n_chunks * n_tg * g.tg * g.nt * g.ck * planes;
-  const size_t esz = planes == 2 ? 2 : ek_size(ek);
-  const size_t plane_el = (size_t)g.tg * g.nt * g.ck;
-  out.assign(n_el * esz, 0);
-  for (int nt = 0; nt < n_tiles; ++nt)
-    for (int ch = 0; ch < n_chunks; ++ch)
-      for (int tg = 0; tg < n_tg; ++tg)
-        for (int t = 0; t < g.tg; ++t) {
-          const int tap = tg * g.tg + t, dy = tap / ks, dx = tap % ks;
-          const int rowb = g.ck * (int)esz, ppp = rowb / 16, rpb = 256 / rowb, epp = 16 / (int)esz;
-          const size_t blk0 = (((size_t)(nt * n_chunks + ch) * n_tg + tg) * g.tg + 0) * (size_t)g.nt * g.ck * planes;
-          for (int n = 0; n < g.nt; ++n)
-            for (int k = 0; k < g.ck; ++k) {
-              const int co = nt * g.nt + n, ci = ch * g.ck + k;
-              // element index inside the packed image; v2 XORs the 16-B piece index with the row swizzle
-              const int row = t * g.nt + n;
-              const int piece = k / epp, within = k % epp;
-              const int piece_sw = swizzle ? (piece ^ ((row / rpb) & (ppp - 1))) : piece;
-              const size_t idx = blk0 + (size_t)row * g.ck + (size_t)piece_sw * epp + within;
-              const float v = (co < g.cout) ? w_oihw[(((size_t)co * g.cin + ci) * ks + dy) * ks + dx] : 0.f;
-              if (g.stack && co >= g.cout && co < 2 * g.cout) {
-                // stacked image (conv4, EK_F16R): cout row cout + c = the lo half of row c times STACK_LSCALE (pack_weights_kernel's arithmetic)
-                const float wv = w_oihw[(((size_t)(co - g.cout) * g.cin + ci) * ks + dy) * ks + dx];
-                if (!(std::fabs(wv) < 60000.f)) fits = false;
-                const uint16_t u = host_f32_to_f16((wv - (float)(_Float16)wv) * STACK_LSCALE);
-                std::memcpy(&out[idx * 2], &u, 2);
-                continue;
-              }
-              if (planes == 2) {
-                // hi = f16(w * SPLIT_WSCALE), lo = f16(w * SPLIT_WSCALE - hi): the same arithmetic as pack_weights_kernel (dd_misc.hip)
-                const float vs = v * SPLIT_WSCALE;
-                if (!(std::fabs(vs) < 60000.f)) fits = false;       // |w| >= 234: beyond f16 after scaling (reported by the caller)
-                const _Float16 hi = (_Float16)vs;
-                const _Float16 lo = (_Float16)(vs - (float)hi);
-                std::memcpy(&out[idx * 2], &hi, 2);
-                std::memcpy(&out[(idx + plane_el) * 2], &lo, 2);
-              } else if (ek == EK_F32) std::memcpy(&out[idx * 4], &v, 4);
-              else {
-                const uint16_t u = (ek == EK_BF16) ? host_f32_to_bf16(v) : host_f32_to_f16(v);
-                std::memcpy(&out[idx * 2], &u, 2);
-              }
-            }
-        }
-  return fits;
-}
-
-int upload(dd_handle_t h, DevBuf& dst, const void* src, size_t bytes, hipStream_t s) {
-  if (dst.bytes < bytes || !dst.p) DD_HIP(dst.alloc(bytes));
-  DD_HIP(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, s));
-  return DD_OK;
-}
 }  // namespace ddapi
 
 extern "C" {
@@ -199,78 +140,117 @@ int dd_set_weight_device(dd_handle_t h, const char* name, const float* data, int
   return h->fail(DD_ERR_INVALID_ARG, std::string("dd_set_weight_device: unknown parameter name '") + name + "'");
 }
 }  // extern "C"
-
 namespace ddapi {
 
-// host_w <- the device copies that are newer (mixed host / device updates of one group, and the host-only consumers: Winograd images)
-int pull_device_weights_to_host(dd_handle_t h, hipStream_t s) {
-  if (h->dev_newer.empty()) return DD_OK;
-  DD_HIP(hipStreamSynchronize(s));
-  for (const std::string& name : h->dev_newer) {
-    const DevBuf& b = *h->dev_w[name];
-    std::vector<float>& v = h->host_w[name];
-    v.resize(b.bytes / 4);
-    DD_HIP(hipMemcpy(v.data(), b.p, b.bytes, hipMemcpyDeviceToHost));
-  }
-  h->dev_newer.clear();
-  return DD_OK;
-}
-
 // The packed-image geometry of kernel (kid, ek).  A pair no kernel runs (conv_pack_geom2's all-zero answer: a mistyped id, a kind the form does
-// not exist in) fails the call here -- it must not travel on as a zero-sized image, nor on pack_conv_weights' "does not fit the split image" signal.
+// not exist in) fails the call here -- it must not travel on as a zero-sized image.
 int pack_geom(dd_handle_t h, int kid, int ek, PackGeom* g) {
   *g = conv_pack_geom2(kid, ek);
   if (g->cout == 0) return h->fail(DD_ERR_INVALID_ARG, "no fused convolution kernel, hence no packed weight image, for kernel id " + std::to_string(kid) + " in element kind " + std::to_string(ek));
   return DD_OK;
 }
-// Host route: one weight tensor into the packed image of kernel (kid, ek), uploaded to dst; *fits is cleared when a weight does not fit the split-f16 image
-static int pack_upload(dd_handle_t h, const float* w, int kid, int ek, DevBuf& dst, hipStream_t s, bool* fits = nullptr) {
-  PackGeom g;
-  DD_TRY(pack_geom(h, kid, ek, &g));
-  std::vector<uint8_t> packed;
-  if (!pack_conv_weights(w, g, ek, true, packed) && fits) *fits = false;
-  DD_TRY(upload(h, dst, packed.data(), packed.size(), s));
-  DD_HIP(hipStreamSynchronize(s));     // `packed` is a temporary
-  return DD_OK;
-}
 
-int ensure_bytes(dd_handle_t h, DevBuf& dst, size_t bytes) {
+// `dst` holds at least `bytes` (a buffer that is large enough keeps its address: graphs hold it); with `src`, it is filled from that host array
+// on stream `s` -- asynchronously: the array stays untouched until the stream has been synchronised (dd_commit_weights does, once, at its end)
+int device_buf(dd_handle_t h, DevBuf& dst, size_t bytes, const void* src, hipStream_t s) {
   if (dst.bytes < bytes || !dst.p) DD_HIP(dst.alloc(bytes));
+  if (src) DD_HIP(hipMemcpyAsync(dst.p, src, bytes, hipMemcpyHostToDevice, s));
   return DD_OK;
 }
 
-// One convolution's weights from a device fp32 OIHW tensor into every layout the forward / backward kernels read -- the device twin of the
-// host loops in dd_commit_weights (same geometries, same buffers), all on stream `s`.
-int pack_conv_layer_device(dd_handle_t h, ConvLayer& L, const float* w, int fwd_layer, int dgrad_layer, bool with_naive, hipStream_t s) {
-  for (int wi = 0; wi < NUM_WIMG; ++wi) {
-    if (!wimg_has(wi, fwd_layer)) continue;
-    const int ek = wimg_kind(wi);
-    PackGeom g2, gt;
-    int rc = pack_geom(h, fwd_layer, ek, &g2); if (rc) return rc;
-    rc = ensure_bytes(h, L.wpack2[wi], pack_weights_bytes(g2, ek)); if (rc) return rc;
-    DD_HIP(launch_pack_weights(w, L.wpack2[wi].p, g2, ek, true, false, s));
-    if (wi == WIMG_SPLIT || wi == WIMG_STACK) continue;           // the split / refined f16 modes are forward only
-    rc = pack_geom(h, dgrad_layer, ek, &gt); if (rc) return rc;
-    rc = ensure_bytes(h, L.wpackT[ek], pack_weights_bytes(gt, ek)); if (rc) return rc;
-    DD_HIP(launch_pack_weights(w, L.wpackT[ek].p, gt, ek, true, true, s));
+// One device fp32 tensor W[cout][cin][ks][ks] of `numel` elements into the weight images of kernel `kid`: image slot slots[i] (element kind
+// wimg_kind) into images[slots[i]], by pack_weights_kernel (dd_misc.hip) -- the one place that knows the layout
+//   [n_tile][cin_chunk][tap_group][tap_in_group][n (NT)][k (CK)], zero beyond cout, 16-byte pieces swizzled for the LDS-DMA,
+// the 16-bit roundings, the split-f16 pair and conv4's stacked lo halves.  transposed: the images of the data-gradient convolution of W.
+// The kernel indexes the tensor by the geometry of (kid, kind): a tensor of another size fails the call before anything is read.
+int pack_images(dd_handle_t h, const float* w, int64_t numel, int kid, const int* slots, int n_slots, DevBuf* images, bool transposed, hipStream_t s) {
+  for (int i = 0; i < n_slots; ++i) {
+    const int ek = wimg_kind(slots[i]);
+    PackGeom g;
+    DD_TRY(pack_geom(h, kid, ek, &g));
+    if (numel != (int64_t)g.cout * g.cin * g.ks * g.ks)
+      return h->fail(DD_ERR_INVALID_ARG, "weight image of kernel id " + std::to_string(kid) + " in element kind " + std::to_string(ek) + " packs " +
+                                             std::to_string((int64_t)g.cout * g.cin * g.ks * g.ks) + " weights, the tensor has " + std::to_string(numel));
+    DD_TRY(device_buf(h, images[slots[i]], pack_weights_bytes(g, ek)));
+    DD_HIP(launch_pack_weights(w, images[slots[i]].p, g, ek, true, transposed, s));
   }
+  return DD_OK;
+}
+
+namespace {
+
+// eval-mode BatchNorm `pre` (.weight / .bias / .running_mean / .running_var) of C channels as y = x * scale + shift.  The scale stays in double:
+// it multiplies the convolution's weights in double (FPN, neck); the codec rounds it to float first.
+void bn_fold(dd_handle_t h, const std::string& pre, int C, std::vector<double>& scale, std::vector<float>& shift) {
+  const auto &g = h->host_w[pre + ".weight"], &b = h->host_w[pre + ".bias"], &m = h->host_w[pre + ".running_mean"], &v = h->host_w[pre + ".running_var"];
+  scale.resize(C); shift.resize(C);
+  for (int c = 0; c < C; ++c) {
+    scale[c] = (double)g[c] / std::sqrt((double)v[c] + (double)BN_EPS);
+    shift[c] = (float)((double)b[c] - (double)m[c] * scale[c]);
+  }
+}
+
+// What one dd_commit_weights call shares between its groups: the stream, the host arrays its asynchronous uploads read (alive until the call
+// has synchronised the stream) and, per packed group, the device word that collects max |w| of the tensors that were packed.
+struct Commit {
+  dd_handle_t h;
+  hipStream_t s;
+  std::list<std::vector<float>> held;
+  enum { FIT_MODEL, FIT_FPN, FIT_NECK, N_FIT };
+};
+
+// `v` into `dst` on the call's stream; the call keeps the array until it has synchronised
+int upload_held(Commit& c, DevBuf& dst, std::vector<float>&& v) {
+  c.held.push_back(std::move(v));
+  return device_buf(c.h, dst, c.held.back().size() * 4, c.held.back().data(), c.s);
+}
+
+// A folded (BatchNorm-scaled, channel-padded) fp32 tensor: through the handle's staging buffer into the images fp32 / bf16 / f16 / split f16 of
+// kernel `kid`, its magnitude into the group's max-|w| word.  Stream order keeps the next tensor's upload behind this one's pack kernels.
+int pack_folded(Commit& c, std::vector<float>&& w, int kid, DevBuf* images, int fit) {
+  dd_handle_t h = c.h;
+  const int64_t numel = (int64_t)w.size();
+  DD_TRY(upload_held(c, h->stage, std::move(w)));
+  DD_HIP(launch_max_abs(h->stage.as<float>(), numel, h->wmax.as<unsigned>() + fit, c.s));
+  return pack_images(h, h->stage.as<float>(), numel, kid, kImageSlots, 4, images, false, c.s);
+}
+
+// One convolution of the denoiser from its fp32 device tensor into every layout the forward / backward kernels read
+int pack_conv_layer(Commit& c, ConvLayer& L, const float* w, int fwd_layer, int dgrad_layer, bool with_naive) {
+  dd_handle_t h = c.h;
+  const int64_t numel = (int64_t)L.cout * L.cin * 9;
+  int fwd[NUM_WIMG], n_fwd = 0;
+  for (int wi = 0; wi < NUM_WIMG; ++wi)
+    if (wimg_has(wi, fwd_layer)) fwd[n_fwd++] = wi;
+  DD_TRY(pack_images(h, w, numel, fwd_layer, fwd, n_fwd, L.wpack2, false, c.s));
+  DD_TRY(pack_images(h, w, numel, dgrad_layer, kImageSlots, NUM_EK, L.wpackT, true, c.s));      // (the split / refined f16 modes are forward only)
+  DD_HIP(launch_max_abs(w, numel, h->wmax.as<unsigned>() + Commit::FIT_MODEL, c.s));
+  DD_TRY(device_buf(h, L.w_oihw, (size_t)numel * 4));        // fp32 OIHW: the naive path, the E[t] tables, the hoisted Swin form's composition
+  DD_HIP(hipMemcpyAsync(L.w_oihw.p, w, (size_t)numel * 4, hipMemcpyDeviceToDevice, c.s));
   if (with_naive) {
-    const size_t bytes = (size_t)L.cout * L.cin * 9 * 4;
-    int rc = ensure_bytes(h, L.w_oihw, bytes); if (rc) return rc;
-    rc = ensure_bytes(h, L.wT_oihw, bytes); if (rc) return rc;
-    DD_HIP(hipMemcpyAsync(L.w_oihw.p, w, bytes, hipMemcpyDeviceToDevice, s));
-    DD_HIP(launch_transpose_flip(w, L.wT_oihw.as<float>(), L.cout, L.cin, 9, s));
+    DD_TRY(device_buf(h, L.wT_oihw, (size_t)numel * 4));
+    DD_HIP(launch_transpose_flip(w, L.wT_oihw.as<float>(), L.cout, L.cin, 9, c.s));
   }
   return DD_OK;
 }
 
-// The denoiser group when every one of its parameters came through dd_set_weight_device: no host copy is touched.
-int commit_model_from_device(dd_handle_t h, hipStream_t s) {
+// ---- denoiser (model.*): the newest value of every parameter, whichever call delivered it, as an fp32 device tensor; from there the pack kernels ----
+int commit_model(Commit& c) {
+  dd_handle_t h = c.h;
+  hipStream_t s = c.s;
+  for (const auto& ws : required_weights(h->variant, h->fpn_pyramid)) {
+    if (weight_group(ws.name) != 0 || h->dev_newer.count(ws.name)) continue;
+    std::unique_ptr<DevBuf>& b = h->dev_w[ws.name];
+    if (!b) b.reset(new DevBuf());
+    if (b->bytes != (size_t)ws.numel * 4) DD_HIP(b->alloc((size_t)ws.numel * 4));
+    DD_HIP(hipMemcpyAsync(b->p, h->host_w[ws.name].data(), (size_t)ws.numel * 4, hipMemcpyHostToDevice, s));     // (host_w outlives the call)
+    h->dev_newer.insert(ws.name);
+  }
   auto D = [&](const std::string& n) { return h->dev_w[n]->as<float>(); };
   auto copy_small = [&](DevBuf& dst, const std::string& n, size_t pad_elems) -> int {
     const DevBuf& src = *h->dev_w[n];
     const size_t bytes = std::max(src.bytes, pad_elems * 4);
-    int rc = ensure_bytes(h, dst, bytes); if (rc) return rc;
+    DD_TRY(device_buf(h, dst, bytes));
     if (bytes > src.bytes) DD_HIP(hipMemsetAsync(dst.p, 0, bytes, s));
     DD_HIP(hipMemcpyAsync(dst.p, src.p, src.bytes, hipMemcpyDeviceToDevice, s));
     return DD_OK;
@@ -278,10 +258,10 @@ int commit_model_from_device(dd_handle_t h, hipStream_t s) {
   for (int l = 0; l < 4; ++l) {
     ConvLayer& L = h->L[l];
     L.cin = kCins[l]; L.cout = kCouts[l];
-    int rc = pack_conv_layer_device(h, L, D(std::string(kConvNames[l]) + ".weight"), kid_denoiser(l), kid_dgrad(l), true, s); if (rc) return rc;
-    rc = copy_small(L.bias, std::string(kConvNames[l]) + ".bias", 32); if (rc) return rc;
-    rc = copy_small(L.gamma, std::string(kGnNames[l]) + ".weight", 0); if (rc) return rc;
-    rc = copy_small(L.beta, std::string(kGnNames[l]) + ".bias", 0); if (rc) return rc;
+    DD_TRY(pack_conv_layer(c, L, D(std::string(kConvNames[l]) + ".weight"), kid_denoiser(l), kid_dgrad(l), true));
+    DD_TRY(copy_small(L.bias, std::string(kConvNames[l]) + ".bias", 32));
+    DD_TRY(copy_small(L.gamma, std::string(kGnNames[l]) + ".weight", 0));
+    DD_TRY(copy_small(L.beta, std::string(kGnNames[l]) + ".bias", 0));
   }
   if (h->variant == DD_VARIANT_SWIN) {
     const char* names[2] = {"model.upsample_fuse.convA.conv", "model.upsample_fuse.convB.conv"};
@@ -289,278 +269,180 @@ int commit_model_from_device(dd_handle_t h, hipStream_t s) {
     for (int i = 0; i < 2; ++i) {
       ConvLayer& L = *Ls[i];
       L.cin = COND_C; L.cout = COND_C;
-      int rc = pack_conv_layer_device(h, L, D(std::string(names[i]) + ".weight"), kid_swin_fuse(i), KID_SWIN_CONVB, false, s); if (rc) return rc;
-      rc = ensure_bytes(h, L.w_oihw, (size_t)COND_C * COND_C * 9 * 4); if (rc) return rc;      // fp32 OIHW: the hoisted form's E[t] tables / 5x5 composition
-      DD_HIP(hipMemcpyAsync(L.w_oihw.p, D(std::string(names[i]) + ".weight"), (size_t)COND_C * COND_C * 9 * 4, hipMemcpyDeviceToDevice, s));
-      rc = copy_small(L.bias, std::string(names[i]) + ".bias", 0); if (rc) return rc;
+      // backward: the data gradient of a 256 -> 256 convolution = the convB kernel (raw input, no norm) on W^T flipped
+      DD_TRY(pack_conv_layer(c, L, D(std::string(names[i]) + ".weight"), kid_swin_fuse(i), KID_SWIN_CONVB, false));
+      DD_TRY(copy_small(L.bias, std::string(names[i]) + ".bias", 0));
     }
   }
-  int rc = copy_small(h->emb, "model.time_embedding.weight", 0); if (rc) return rc;
+  DD_TRY(copy_small(h->emb, "model.time_embedding.weight", 0));
   if (h->etab.bytes == 0) {
     DD_HIP(h->etab.alloc((size_t)EMB_ROWS * 10 * HID_C * 4));
     DD_HIP(h->zero_bias.alloc(COND_C * 4));
     DD_HIP(hipMemsetAsync(h->zero_bias.p, 0, COND_C * 4, s));
   }
   DD_HIP(launch_etab(h->L[2].w_oihw.as<float>(), h->emb.as<float>(), h->etab.as<float>(), s));
-  // do the forward weights fit the split-f16 images?  (the host route checks while packing; here: one max-|w| reduction per tensor)
-  if (!h->wmax.p) DD_HIP(h->wmax.alloc(sizeof(unsigned)));
-  DD_HIP(hipMemsetAsync(h->wmax.p, 0, sizeof(unsigned), s));
-  for (int l = 0; l < 4; ++l)
-    DD_HIP(launch_max_abs(D(std::string(kConvNames[l]) + ".weight"), (long long)kCouts[l] * kCins[l] * 9, h->wmax.as<unsigned>(), s));
-  if (h->variant == DD_VARIANT_SWIN) {
-    DD_HIP(launch_max_abs(D("model.upsample_fuse.convA.conv.weight"), (long long)COND_C * COND_C * 9, h->wmax.as<unsigned>(), s));
-    DD_HIP(launch_max_abs(D("model.upsample_fuse.convB.conv.weight"), (long long)COND_C * COND_C * 9, h->wmax.as<unsigned>(), s));
-  }
-  unsigned wbits = 0;
-  DD_HIP(hipMemcpyAsync(&wbits, h->wmax.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  DD_HIP(hipStreamSynchronize(s));     // as the host route: the new images are in place when the call returns, whatever stream runs next
-  float wmax_f;
-  std::memcpy(&wmax_f, &wbits, 4);
-  h->split_ok = wmax_f * SPLIT_WSCALE < 60000.f;       // (false for NaN)
   return DD_OK;
 }
 
-}  // namespace ddapi
-
-extern "C" {
-
-int dd_commit_weights(dd_handle_t h, void* stream) {
-  if (!h) return DD_ERR_INVALID_ARG;
-  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  DD_HIP(hipSetDevice(h->device));
-  // independent groups: "model." (denoiser), "depth_transform." (codec) and "conv_lateral." / "conv_up." (condition FPN,
-  // Res variant).  A group is packed when all of its keys are present; a partially provided group is an error; at least
-  // one must be complete.
-  int have[4] = {0, 0, 0, 0}, need[4] = {0, 0, 0, 0}, n_dev = 0, n_host = 0;     // n_dev / n_host: denoiser parameters whose newest value is on the device / host
-  std::string first_missing[4];
-  for (const auto& ws : required_weights(h->variant, h->fpn_pyramid)) {
-    const int grp = weight_group(ws.name);
-    need[grp]++;
-    if (h->host_w.count(ws.name) || h->dev_newer.count(ws.name)) have[grp]++;
-    else if (first_missing[grp].empty()) first_missing[grp] = ws.name;
-    if (grp == 0) { if (h->dev_newer.count(ws.name)) n_dev++; else n_host++; }
+// ---- condition FPN: eval-mode BatchNorm folded into the (bias-free) convolutions on the host, packed for the fused kernels on the device ----
+int commit_fpn(Commit& c) {
+  dd_handle_t h = c.h;
+  const int* cin = fpn_cin(h->variant, h->fpn_pyramid);
+  const int* cin_pad = fpn_cin_pad(h->variant, h->fpn_pyramid);      // zero weights for the padding channels
+  std::vector<double> sc; std::vector<float> sh;
+  for (int i = 0; i < FPN_LEVELS; ++i) {
+    const std::string pre = "conv_lateral." + std::to_string(i);
+    bn_fold(h, pre + ".1", COND_C, sc, sh);
+    const std::vector<float>& w0 = h->host_w[pre + ".0.weight"];    // [256][cin][3][3]
+    const size_t per = (size_t)cin[i] * 9, per_pad = (size_t)cin_pad[i] * 9;
+    std::vector<float> w((size_t)COND_C * per_pad, 0.f);
+    for (int co = 0; co < COND_C; ++co)
+      for (size_t k = 0; k < per; ++k) w[co * per_pad + k] = (float)((double)w0[co * per + k] * sc[co]);
+    DD_TRY(pack_folded(c, std::move(w), kid_fpn_lateral(pyramid_of(h->variant, h->fpn_pyramid), i), h->fpn_lat_w[i], Commit::FIT_FPN));
+    DD_TRY(upload_held(c, h->fpn_lat_b[i], std::move(sh)));
   }
-  for (int grp = 0; grp < 4; ++grp)
-    if (have[grp] != 0 && have[grp] != need[grp])
-      return h->fail(DD_ERR_STATE, "dd_commit_weights: missing parameter '" + first_missing[grp] + "'");
-  if (have[0] == 0 && have[1] == 0 && have[2] == 0 && have[3] == 0) return h->fail(DD_ERR_STATE, "dd_commit_weights: no parameters were set");
-  // only the groups that changed since their last commit (dd_set_weight / dd_set_weight_device clear the group's flag)
-  bool do_model = have[0] == need[0] && !h->committed;
-  const bool do_codec = have[1] == need[1] && !h->codec_committed, do_fpn = need[2] > 0 && have[2] == need[2] && !h->fpn_committed;
-  const bool do_neck = need[3] > 0 && have[3] == need[3] && !h->neck_committed;
-  if (!do_model && !do_codec && !do_fpn && !do_neck) return DD_OK;
-  // graphs bake weight pointers; buffers are reused when sizes match, so existing graphs stay valid,
-  // but make sure nothing is in flight while we overwrite them.
-  DD_HIP(hipDeviceSynchronize());
-  if (do_model && n_dev > 0) {
-    if (n_host == 0) {
-      // every denoiser parameter came through dd_set_weight_device: fp32 -> kernel layouts by the pack kernels, all on `s`
-      int rc = commit_model_from_device(h, s); if (rc) return rc;
-      h->committed = true;
-      do_model = false;
-    } else {
-      int rc = pull_device_weights_to_host(h, s); if (rc) return rc;            // mixed update: newest values to the host, host route
-    }
-  }
-  bool split_fits = true;       // every forward weight fits the split-f16 image (checked while packing, reported once the group is through)
-  const char* conv_names[4] = {"model.noise_embedding.0", "model.noise_embedding.3", "model.pred.0", "model.pred.3"};
-  const char* gn_names[4] = {"model.noise_embedding.1", "model.noise_embedding.4", "model.pred.1", "model.pred.4"};
-  const int cins[4] = {LATENT_C, HID_C, COND_C, HID_C}, couts[4] = {HID_C, COND_C, HID_C, LATENT_C};
-  for (int l = 0; do_model && l < 4; ++l) {
-    ConvLayer& L = h->L[l];
-    L.cin = cins[l]; L.cout = couts[l];
-    const std::vector<float>& w = h->host_w[std::string(conv_names[l]) + ".weight"];
-    const std::vector<float>& b = h->host_w[std::string(conv_names[l]) + ".bias"];
-    for (int wi = 0; wi < NUM_WIMG; ++wi) {
-      if (!wimg_has(wi, kid_denoiser(l))) continue;
-      DD_TRY(pack_upload(h, w.data(), kid_denoiser(l), wimg_kind(wi), L.wpack2[wi], s, &split_fits));
-    }
-    std::vector<float> bpad(std::max(32, L.cout), 0.f);
-    std::copy(b.begin(), b.end(), bpad.begin());
-    int rc = upload(h, L.bias, bpad.data(), bpad.size() * 4, s); if (rc) return rc;
-    rc = upload(h, L.w_oihw, w.data(), w.size() * 4, s); if (rc) return rc;
-
-    {
-      std::vector<float> wt(w.size());
-      for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < L.cin; ++ci)
-          for (int k = 0; k < 9; ++k) wt[((size_t)ci * L.cout + co) * 9 + (8 - k)] = w[((size_t)co * L.cin + ci) * 9 + k];
-      rc = upload(h, L.wT_oihw, wt.data(), wt.size() * 4, s); if (rc) return rc;
-      DD_HIP(hipStreamSynchronize(s));
-      for (int ek = 0; ek < NUM_EK; ++ek) DD_TRY(pack_upload(h, wt.data(), kid_dgrad(l), ek, L.wpackT[ek], s));
-    }
-    const std::vector<float>& gg = h->host_w[std::string(gn_names[l]) + ".weight"];
-    const std::vector<float>& gb = h->host_w[std::string(gn_names[l]) + ".bias"];
-    rc = upload(h, L.gamma, gg.data(), gg.size() * 4, s); if (rc) return rc;
-    rc = upload(h, L.beta, gb.data(), gb.size() * 4, s); if (rc) return rc;
-    DD_HIP(hipStreamSynchronize(s));
-  }
-  if (do_model && h->variant == DD_VARIANT_SWIN) {
-    const char* names[2] = {"model.upsample_fuse.convA.conv", "model.upsample_fuse.convB.conv"};
-    ConvLayer* Ls[2] = {&h->LA, &h->LB};
-    for (int i = 0; i < 2; ++i) {
-      ConvLayer& L = *Ls[i];
-      L.cin = COND_C; L.cout = COND_C;
-      const std::vector<float>& w = h->host_w[std::string(names[i]) + ".weight"];
-      const std::vector<float>& b = h->host_w[std::string(names[i]) + ".bias"];
-      for (int wi = 0; wi < NUM_WIMG; ++wi) {
-        if (!wimg_has(wi, kid_swin_fuse(i))) continue;
-        DD_TRY(pack_upload(h, w.data(), kid_swin_fuse(i), wimg_kind(wi), L.wpack2[wi], s, &split_fits));
-      }
-      int rc = upload(h, L.bias, b.data(), b.size() * 4, s); if (rc) return rc;
-      rc = upload(h, L.w_oihw, w.data(), w.size() * 4, s); if (rc) return rc;       // fp32 OIHW: the hoisted form's E[t] tables (swin_ttab)
-      DD_HIP(hipStreamSynchronize(s));
-      // backward: data gradient of a 256->256 conv = the convB kernel (layer 6: raw input, no norm) on W^T flipped
-      std::vector<float> wt(w.size());
-      for (int co = 0; co < COND_C; ++co)
+  for (int j = 0; j < FPN_LEVELS - 1; ++j) {
+    const std::string pre = "conv_up." + std::to_string(j);
+    bn_fold(h, pre + ".1", COND_C, sc, sh);
+    const std::vector<float>& wt = h->host_w[pre + ".0.weight"];     // ConvTranspose2d weight [cin][cout][2][2]
+    // as a 1x1 convolution with 4 x 256 outputs: row (dy*2+dx)*256 + co, column ci
+    std::vector<float> w((size_t)4 * COND_C * COND_C), b4((size_t)4 * COND_C);
+    for (int par = 0; par < 4; ++par)
+      for (int co = 0; co < COND_C; ++co) {
+        b4[par * COND_C + co] = sh[co];
         for (int ci = 0; ci < COND_C; ++ci)
-          for (int k = 0; k < 9; ++k) wt[((size_t)ci * COND_C + co) * 9 + (8 - k)] = w[((size_t)co * COND_C + ci) * 9 + k];
-      for (int ek = 0; ek < NUM_EK; ++ek) DD_TRY(pack_upload(h, wt.data(), KID_SWIN_CONVB, ek, L.wpackT[ek], s));
-    }
-  }
-  if (do_model) {
-    h->split_ok = split_fits;      // a weight of magnitude >= 234 does not fit the split-f16 images: only the split modes refuse such parameters (check_split)
-    const std::vector<float>& e = h->host_w["model.time_embedding.weight"];
-    int rc = upload(h, h->emb, e.data(), e.size() * 4, s); if (rc) return rc;
-    DD_HIP(hipStreamSynchronize(s));
-    if (h->etab.bytes == 0) {
-      DD_HIP(h->etab.alloc((size_t)EMB_ROWS * 10 * HID_C * 4));
-      DD_HIP(h->zero_bias.alloc(COND_C * 4));
-      DD_HIP(hipMemsetAsync(h->zero_bias.p, 0, COND_C * 4, s));
-    }
-    DD_HIP(launch_etab(h->L[2].w_oihw.as<float>(), h->emb.as<float>(), h->etab.as<float>(), s));
-    DD_HIP(hipStreamSynchronize(s));
-    h->committed = true;
-  }
-  if (do_fpn) {
-    // ---- condition FPN: fold eval-mode BatchNorm into the (bias-free) convolutions, pack for the v2 kernels ----
-    auto fold = [&](const std::string& pre, std::vector<double>& scale, std::vector<float>& shift) {
-      const auto &g = h->host_w[pre + ".weight"], &b = h->host_w[pre + ".bias"], &m = h->host_w[pre + ".running_mean"],
-                 &v = h->host_w[pre + ".running_var"];
-      scale.resize(COND_C); shift.resize(COND_C);
-      for (int c = 0; c < COND_C; ++c) {
-        scale[c] = (double)g[c] / std::sqrt((double)v[c] + (double)BN_EPS);
-        shift[c] = (float)((double)b[c] - (double)m[c] * scale[c]);
+          w[((size_t)par * COND_C + co) * COND_C + ci] = (float)((double)wt[((size_t)ci * COND_C + co) * 4 + par] * sc[co]);
       }
-    };
-    std::vector<double> sc; std::vector<float> sh;
-    bool fpn_fits = true;
-    for (int i = 0; i < FPN_LEVELS; ++i) {
-      const std::string pre = "conv_lateral." + std::to_string(i);
-      fold(pre + ".1", sc, sh);
-      const std::vector<float>& w0 = h->host_w[pre + ".0.weight"];    // [256][cin][3][3]
-      const size_t per = (size_t)fpn_cin(h->variant, h->fpn_pyramid)[i] * 9;
-      const size_t per_pad = (size_t)fpn_cin_pad(h->variant, h->fpn_pyramid)[i] * 9;      // zero weights for the padding channels
-      std::vector<float> w((size_t)COND_C * per_pad, 0.f);
-      for (int co = 0; co < COND_C; ++co)
-        for (size_t k = 0; k < per; ++k) w[co * per_pad + k] = (float)((double)w0[co * per + k] * sc[co]);
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi)        // fp32, bf16, f16 and the split-f16 image (the split / refined modes' pyramid)
-        DD_TRY(pack_upload(h, w.data(), kid_fpn_lateral(pyramid_of(h->variant, h->fpn_pyramid), i), wimg_kind(wi), h->fpn_lat_w[i][wi], s, &fpn_fits));
-      int rc = upload(h, h->fpn_lat_b[i], sh.data(), sh.size() * 4, s); if (rc) return rc;
-      DD_HIP(hipStreamSynchronize(s));
-    }
-    for (int j = 0; j < FPN_LEVELS - 1; ++j) {
-      const std::string pre = "conv_up." + std::to_string(j);
-      fold(pre + ".1", sc, sh);
-      const std::vector<float>& wt = h->host_w[pre + ".0.weight"];     // ConvTranspose2d weight [cin][cout][2][2]
-      // as a 1x1 convolution with 4 x 256 outputs: row (dy*2+dx)*256 + co, column ci
-      std::vector<float> w((size_t)4 * COND_C * COND_C);
-      std::vector<float> b4((size_t)4 * COND_C);
-      for (int par = 0; par < 4; ++par)
-        for (int co = 0; co < COND_C; ++co) {
-          b4[par * COND_C + co] = sh[co];
-          for (int ci = 0; ci < COND_C; ++ci)
-            w[((size_t)par * COND_C + co) * COND_C + ci] = (float)((double)wt[((size_t)ci * COND_C + co) * 4 + par] * sc[co]);
-        }
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_TRY(pack_upload(h, w.data(), KID_FPN_UP, wimg_kind(wi), h->fpn_up_w[j][wi], s, &fpn_fits));
-      int rc = upload(h, h->fpn_up_b[j], b4.data(), b4.size() * 4, s); if (rc) return rc;
-      DD_HIP(hipStreamSynchronize(s));
-    }
-    h->fpn_split_ok = fpn_fits;      // a folded weight beyond the split image's range: the split / refined modes keep the fp32-operand kernels for the pyramid
-    h->fpn_committed = true;
+    DD_TRY(pack_folded(c, std::move(w), KID_FPN_UP, h->fpn_up_w[j], Commit::FIT_FPN));
+    DD_TRY(upload_held(c, h->fpn_up_b[j], std::move(b4)));
   }
-  if (do_neck) {
-    // ---- HAHI neck: fold eval-mode BatchNorm into the bias-free convolutions (scale into the weights, shift = bias), pack ----
-    // The kernels' channel counts can exceed the reference's (MPViT level 1: 216 carried as 224): the folded weights are laid into
-    // [cout_k][cin_k] with zeros in the padding; a fusion convolution reads the concatenation [lateral (Ck) | projection (512)] (level 0:
-    // [projection | lateral]), so its reference input channel ci >= C of the lateral part's successor moves up by Ck - C.
-    bool neck_fits = true;
-    for (const NeckConv& c : neck_convs(h->fpn_pyramid)) {
-      const auto &g = h->host_w[c.name + ".bn.weight"], &b = h->host_w[c.name + ".bn.bias"], &m = h->host_w[c.name + ".bn.running_mean"],
-                 &v = h->host_w[c.name + ".bn.running_var"];
-      const std::vector<float>& w0 = h->host_w[c.name + ".conv.weight"];
-      PackGeom pg;
-      DD_TRY(pack_geom(h, c.layer, EK_F32, &pg));
-      const int kk = c.ks * c.ks, cin_k = pg.cin, cout_k = pg.cout;
-      std::vector<float> w((size_t)cout_k * cin_k * kk, 0.f), sh((size_t)pg.cout_pad, 0.f);
-      for (int co = 0; co < c.cout; ++co) {
-        const double sc = (double)g[co] / std::sqrt((double)v[co] + (double)BN_EPS);
-        sh[co] = (float)((double)b[co] - (double)m[co] * sc);
-        for (int ci = 0; ci < c.cin; ++ci) {
-          int cik = ci;
-          if (c.kind == NECK_FUSION && c.level > 0 && ci >= c.C) cik = ci - c.C + c.Ck;          // [lateral | projection]: the projection part starts at Ck
-          for (int k = 0; k < kk; ++k)
-            w[((size_t)co * cin_k + cik) * kk + k] = (float)((double)w0[((size_t)co * c.cin + ci) * kk + k] * sc);
-        }
+  return DD_OK;
+}
+
+// ---- HAHI neck: eval-mode BatchNorm folded into the bias-free convolutions (scale into the weights, shift = bias) ----
+// The kernels' channel counts can exceed the reference's (MPViT level 1: 216 carried as 224): the folded weights are laid into
+// [cout_k][cin_k] with zeros in the padding; a fusion convolution reads the concatenation [lateral (Ck) | projection (512)] (level 0:
+// [projection | lateral]), so its reference input channel ci >= C of the lateral part's successor moves up by Ck - C.
+int commit_neck(Commit& c) {
+  dd_handle_t h = c.h;
+  std::vector<double> sc; std::vector<float> sh;
+  for (const NeckConv& nc : neck_convs(h->fpn_pyramid)) {
+    bn_fold(h, nc.name + ".bn", nc.cout, sc, sh);
+    const std::vector<float>& w0 = h->host_w[nc.name + ".conv.weight"];
+    PackGeom pg;
+    DD_TRY(pack_geom(h, nc.layer, EK_F32, &pg));
+    const int kk = nc.ks * nc.ks, cin_k = pg.cin, cout_k = pg.cout;
+    std::vector<float> w((size_t)cout_k * cin_k * kk, 0.f);
+    sh.resize((size_t)pg.cout_pad, 0.f);
+    for (int co = 0; co < nc.cout; ++co)
+      for (int ci = 0; ci < nc.cin; ++ci) {
+        int cik = ci;
+        if (nc.kind == NECK_FUSION && nc.level > 0 && ci >= nc.C) cik = ci - nc.C + nc.Ck;          // [lateral | projection]: the projection part starts at Ck
+        for (int k = 0; k < kk; ++k)
+          w[((size_t)co * cin_k + cik) * kk + k] = (float)((double)w0[((size_t)co * nc.cin + ci) * kk + k] * sc[co]);
       }
-      const int slot = 4 * c.kind + c.level;
-      for (int wi = 0; wi <= WIMG_SPLIT; ++wi) DD_TRY(pack_upload(h, w.data(), c.layer, wimg_kind(wi), h->neck_w[slot][wi], s, &neck_fits));
-      int rc = upload(h, h->neck_b[slot], sh.data(), sh.size() * 4, s); if (rc) return rc;
-      DD_HIP(hipStreamSynchronize(s));
-    }
-    h->neck_split_ok = neck_fits;
-    h->neck_committed = true;
+    const int slot = 4 * nc.kind + nc.level;
+    DD_TRY(pack_folded(c, std::move(w), nc.layer, h->neck_w[slot], Commit::FIT_NECK));
+    DD_TRY(upload_held(c, h->neck_b[slot], std::move(sh)));
   }
-  if (!do_codec) return DD_OK;
-  // ---- codec: fold eval-mode BatchNorm into the convolutions (reference depth_transform.py:15-26) ----
+  return DD_OK;
+}
+
+// ---- codec: eval-mode BatchNorm folded into the convolutions (reference depth_transform.py:15-26), all in one allocation ----
+int commit_codec(Commit& c) {
+  dd_handle_t h = c.h;
   auto W = [&](const char* n) -> const std::vector<float>& { return h->host_w[n]; };
-  auto bn_fold = [&](const std::string& p, std::vector<float>& scale, std::vector<float>& shift) {
-    const auto &g = W((p + ".weight").c_str()), &b = W((p + ".bias").c_str()), &m = W((p + ".running_mean").c_str()),
-               &v = W((p + ".running_var").c_str());
-    scale.resize(16); shift.resize(16);
-    for (int c = 0; c < 16; ++c) {
-      const double sc = (double)g[c] / std::sqrt((double)v[c] + (double)BN_EPS);
-      scale[c] = (float)sc;
-      shift[c] = (float)((double)b[c] - (double)m[c] * sc);
-    }
-  };
   std::vector<float> blob;
   auto push = [&](const std::vector<float>& v) { size_t off = blob.size(); blob.insert(blob.end(), v.begin(), v.end());
                                                  while (blob.size() % 4) blob.push_back(0.f); return off; };
-  std::vector<float> sc, sh;
-  bn_fold("depth_transform.conv_transform.0.1", sc, sh);
+  std::vector<double> scd; std::vector<float> sc, sh;
+  auto fold = [&](const char* pre) { bn_fold(h, pre, 16, scd, sh); sc.assign(16, 0.f); for (int ch = 0; ch < 16; ++ch) sc[ch] = (float)scd[ch]; };      // the codec scales in float
+  fold("depth_transform.conv_transform.0.1");
   std::vector<float> e0 = W("depth_transform.conv_transform.0.0.weight");
-  for (int c = 0; c < 16; ++c) for (int k = 0; k < 9; ++k) e0[c * 9 + k] *= sc[c];
+  for (int ch = 0; ch < 16; ++ch) for (int k = 0; k < 9; ++k) e0[ch * 9 + k] *= sc[ch];
   const size_t o_e0 = push(e0), o_eb0 = push(sh);
-  bn_fold("depth_transform.conv_transform.1.1", sc, sh);
+  fold("depth_transform.conv_transform.1.1");
   std::vector<float> e1 = W("depth_transform.conv_transform.1.0.weight");
   for (int co = 0; co < 16; ++co) for (int k = 0; k < 16 * 9; ++k) e1[co * 144 + k] *= sc[co];
   const size_t o_e1 = push(e1), o_eb1 = push(sh);
   std::vector<float> e1t(2304);          // the same weights tap-major [tap][ci][co] for enc1_kernel
   for (int co = 0; co < 16; ++co) for (int ci = 0; ci < 16; ++ci) for (int k = 0; k < 9; ++k) e1t[(k * 16 + ci) * 16 + co] = e1[(co * 16 + ci) * 9 + k];
   const size_t o_e1t = push(e1t);
-  bn_fold("depth_transform.conv_inv_transform.1", sc, sh);
+  fold("depth_transform.conv_inv_transform.1");
   std::vector<float> d0 = W("depth_transform.conv_inv_transform.0.weight");       // (in, out, 4, 4)
   for (int ci = 0; ci < 16; ++ci) for (int co = 0; co < 16; ++co) for (int k = 0; k < 16; ++k) d0[(ci * 16 + co) * 16 + k] *= sc[co];
   std::vector<float> db0(16);
-  { const auto& cb = W("depth_transform.conv_inv_transform.0.bias"); for (int c = 0; c < 16; ++c) db0[c] = cb[c] * sc[c] + sh[c]; }
+  { const auto& cb = W("depth_transform.conv_inv_transform.0.bias"); for (int ch = 0; ch < 16; ++ch) db0[ch] = cb[ch] * sc[ch] + sh[ch]; }
   const size_t o_d0 = push(d0), o_db0 = push(db0);
   // the same weights tap-major [ky][kx][ci][co] for the fused decoder kernel (a wave reads one (tap, ci) row of 16 couts uniformly)
   std::vector<float> d0t(4096);
   for (int ci = 0; ci < 16; ++ci) for (int co = 0; co < 16; ++co) for (int k = 0; k < 16; ++k) d0t[(k * 16 + ci) * 16 + co] = d0[(ci * 16 + co) * 16 + k];
   const size_t o_d0t = push(d0t);
   const size_t o_d1 = push(W("depth_transform.conv_inv_transform.3.0.weight"));
-  {
-    int rc = upload(h, h->codec_buf, blob.data(), blob.size() * 4, s); if (rc) return rc;
-    DD_HIP(hipStreamSynchronize(s));
-  }
+  DD_TRY(upload_held(c, h->codec_buf, std::move(blob)));
   const float* base = h->codec_buf.as<float>();
   h->codec.enc_w0 = base + o_e0; h->codec.enc_b0 = base + o_eb0;
   h->codec.enc_w1 = base + o_e1; h->codec.enc_b1 = base + o_eb1; h->codec.enc_w1t = base + o_e1t;
   h->codec.dec_w0 = base + o_d0; h->codec.dec_b0 = base + o_db0; h->codec.dec_w0t = base + o_d0t;
   h->codec.dec_w1 = base + o_d1;
   h->codec.dec_b1 = W("depth_transform.conv_inv_transform.3.0.bias")[0];
-  h->codec_committed = true;
+  return DD_OK;
+}
+
+}  // namespace
+}  // namespace ddapi
+
+extern "C" {
+
+int dd_commit_weights(dd_handle_t h, void* stream) {
+  if (!h) return DD_ERR_INVALID_ARG;
+  DD_HIP(hipSetDevice(h->device));
+  // independent groups: "model." (denoiser), "depth_transform." (codec), "conv_lateral." / "conv_up." (condition FPN) and "hahineck." (neck).
+  // A group is packed when all of its keys are present; a partially provided group is an error; at least one must be complete.
+  int have[4] = {0, 0, 0, 0}, need[4] = {0, 0, 0, 0};
+  std::string first_missing[4];
+  for (const auto& ws : required_weights(h->variant, h->fpn_pyramid)) {
+    const int grp = weight_group(ws.name);
+    need[grp]++;
+    if (h->host_w.count(ws.name) || h->dev_newer.count(ws.name)) have[grp]++;
+    else if (first_missing[grp].empty()) first_missing[grp] = ws.name;
+  }
+  for (int grp = 0; grp < 4; ++grp)
+    if (have[grp] != 0 && have[grp] != need[grp])
+      return h->fail(DD_ERR_STATE, "dd_commit_weights: missing parameter '" + first_missing[grp] + "'");
+  if (have[0] == 0 && have[1] == 0 && have[2] == 0 && have[3] == 0) return h->fail(DD_ERR_STATE, "dd_commit_weights: no parameters were set");
+  // only the groups that changed since their last commit (dd_set_weight / dd_set_weight_device clear the group's flag)
+  const bool do_model = have[0] == need[0] && !h->committed, do_codec = have[1] == need[1] && !h->codec_committed;
+  const bool do_fpn = need[2] > 0 && have[2] == need[2] && !h->fpn_committed, do_neck = need[3] > 0 && have[3] == need[3] && !h->neck_committed;
+  if (!do_model && !do_codec && !do_fpn && !do_neck) return DD_OK;
+  // graphs bake weight pointers; buffers are reused when sizes match, so existing graphs stay valid,
+  // but make sure nothing is in flight while we overwrite them.
+  DD_HIP(hipDeviceSynchronize());
+  Commit c{h, reinterpret_cast<hipStream_t>(stream), {}};
+  if (!h->wmax.p) DD_HIP(h->wmax.alloc(Commit::N_FIT * sizeof(unsigned)));
+  DD_HIP(hipMemsetAsync(h->wmax.p, 0, Commit::N_FIT * sizeof(unsigned), c.s));
+  int rc = DD_OK;
+  if (rc == DD_OK && do_model) rc = commit_model(c);
+  if (rc == DD_OK && do_fpn) rc = commit_fpn(c);
+  if (rc == DD_OK && do_neck) rc = commit_neck(c);
+  if (rc == DD_OK && do_codec) rc = commit_codec(c);
+  // one read-back and one synchronisation for the whole call: the images are in place when it returns, whatever stream runs next, and the
+  // host arrays the uploads read (c.held) may go -- also when a group failed half way
+  unsigned wbits[Commit::N_FIT] = {0, 0, 0};
+  hipError_t e = hipMemcpyAsync(wbits, h->wmax.p, sizeof(wbits), hipMemcpyDeviceToHost, c.s);
+  const hipError_t e_sync = hipStreamSynchronize(c.s);
+  h->stage.release();
+  if (rc != DD_OK) return rc;
+  if (e == hipSuccess) e = e_sync;
+  if (e != hipSuccess) return h->fail(DD_ERR_HIP, std::string("dd_commit_weights: ") + hipGetErrorString(e));
+  // do the packed tensors fit the split-f16 images?  |w| x SPLIT_WSCALE must stay inside f16 (|w| < 234; a NaN does not fit).  The denoiser's split
+  // modes (DD_PREC_F16X3 / DD_PREC_F16R) refuse to run on parameters that do not (check_split); the pyramid then keeps the fp32-operand kernels.
+  // conv4's stacked image asks less (|w| inside f16).
+  auto fits = [&](int grp) { float m; std::memcpy(&m, &wbits[grp], 4); return m * SPLIT_WSCALE < 60000.f; };
+  if (do_model) { h->split_ok = fits(Commit::FIT_MODEL); h->committed = true; }
+  if (do_fpn) { h->fpn_split_ok = fits(Commit::FIT_FPN); h->fpn_committed = true; }
+  if (do_neck) { h->neck_split_ok = fits(Commit::FIT_NECK); h->neck_committed = true; }
+  if (do_codec) h->codec_committed = true;
   return DD_OK;
 }
 }  // extern "C"

@@ -5,7 +5,7 @@
 //   activations  NHWC  [B][h][w][C]   element type per precision mode (bf16 / f16 / f32)
 //   state x_t    NHWC  [B][h][w][16]  fp32, ping-pong pair
 //   GroupNorm statistics  [B][DD_STAT_SLOTS][DD_STAT_STRIDE] doubles: per slot (sum, sumsq) x 4 groups
-//   packed conv weights   [n_tile][cin_chunk][tap_group][tap][NT][CK] elements (see pack_conv_weights)
+//   packed conv weights   [n_tile][cin_chunk][tap_group][tap][NT][CK] elements (written by pack_weights_kernel, dd_misc.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -161,7 +161,7 @@ hipError_t launch_conv4_stream(int ek, const ConvParams& p, hipStream_t s, bool 
 hipError_t launch_cadd_reformat(const float* src, void* dst, float* scales, int B, int h, int w, int big, int out_kind, hipStream_t s);
 PackGeom conv_pack_geom2(int layer, int ek);
 
-// ---- weights into kernel layout on the device (dd_misc.hip): the packed image of pack_conv_weights() in dd_api.cpp, bit for bit ----
+// ---- weights into kernel layout (dd_misc.hip): the one packer of every weight image -- denoiser, FPN, neck, hoisted forms; forward and data gradient ----
 size_t pack_weights_bytes(const PackGeom& g, int ek);
 hipError_t launch_pack_weights(const float* src_oihw, void* dst, const PackGeom& g, int ek, bool swizzle, bool transposed, hipStream_t s);
 hipError_t launch_transpose_flip(const float* w, float* wt, int cout, int cin, int kk, hipStream_t s);

@@ -1078,11 +1078,11 @@ hipError_t launch_decode(const CodecWeights& cw, const float* latent_nchw, float
 }
 
 // ------------------------------------------------------------------------------------------------
-// Weights into kernel layout ON THE DEVICE (training: the optimizer updates the fp32 parameters in HBM every step; repacking them
-// on the host costs a D2H copy per tensor plus ~25 ns per packed element, single-threaded, for every element kind and kernel
-// family -- hundreds of ms per iteration).  One thread per PACKED element; same index map, zero padding, LDS swizzle and
-// round-to-nearest-even conversions as the host packer pack_conv_weights() in dd_api.cpp (the two are compared bit for bit in
-// tests/test_library_host_emulation.py).
+// Weights into kernel layout: the one implementation of the packed image (index map, zero padding, LDS swizzle, round-to-nearest-even
+// conversions, split-f16 pair, conv4's stacked lo halves).  Every weight image of the library is written here from an fp32 tensor in HBM
+// (ddapi::pack_images, dd_api_weights.cpp) -- a training step's refreshed parameters without leaving the device, a host array after its upload.
+// One thread per PACKED element.  Checked byte for byte against a NumPy packer (tests/test_igemm2_host_emulation.py) and, through the handle's
+// digest, against what the former host-side packer left (tests/golden/weight_digests.json).
 //   transposed == 0: src = W[cout][cin][ks][ks]
 //   transposed == 1: the data-gradient convolution of W: value(co, ci, dy, dx) = W[ci][co][ks-1-dy][ks-1-dx], W = [g.cin][g.cout][ks][ks]
 // ------------------------------------------------------------------------------------------------
@@ -1114,13 +1114,13 @@ __global__ void __launch_bounds__(256) pack_weights_kernel(const float* __restri
   if (co < g.cout)
     v = transposed ? src[((size_t)ci * g.cout + co) * kk + (kk - 1 - tap)] : src[((size_t)co * g.cin + ci) * kk + tap];
   if (g.stack && co >= g.cout && co < 2 * g.cout) {
-    // stacked image (conv4, EK_F16R): row cout + c = the lo half of row c, times STACK_LSCALE -- the host packer's arithmetic
+    // stacked image (conv4, EK_F16R): row cout + c = the lo half of row c, times STACK_LSCALE
     const float wv = src[((size_t)(co - g.cout) * g.cin + ci) * kk + tap];
     reinterpret_cast<uint16_t*>(dst)[idx] = (uint16_t)f32_to_f16((wv - f16_to_f32(f32_to_f16(wv))) * STACK_LSCALE);
     return;
   }
   if (g.planes > 1) {
-    // hi = f16(w * SPLIT_WSCALE), lo = f16(w * SPLIT_WSCALE - hi): the arithmetic of the host packer (pack_conv_weights in dd_api.cpp)
+    // hi = f16(w * SPLIT_WSCALE), lo = f16(w * SPLIT_WSCALE - hi)
     const float vs = v * SPLIT_WSCALE;
     const uint32_t hi = f32_to_f16(vs);
     reinterpret_cast<uint16_t*>(dst)[idx] = (uint16_t)(lo_plane ? f32_to_f16(vs - f16_to_f32(hi)) : hi);
@@ -1139,8 +1139,8 @@ hipError_t launch_pack_weights(const float* src, void* dst, const PackGeom& g, i
   return hipGetLastError();
 }
 
-// max |w| of a tensor, as the bits of a non-negative float (atomicMax on unsigned keeps the order): the device route's twin of the host
-// packer's "fits the split-f16 image" check (dd_api.cpp: |w| x SPLIT_WSCALE must stay below f16's range)
+// max |w| of a tensor, as the bits of a non-negative float (atomicMax on unsigned keeps the order): the "fits the split-f16 image" check of
+// dd_commit_weights (|w| x SPLIT_WSCALE must stay below f16's range), one word per parameter group
 __global__ void __launch_bounds__(256) max_abs_kernel(const float* __restrict__ w, long long n, unsigned* __restrict__ out) {
   float m = 0.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {

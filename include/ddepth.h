@@ -92,16 +92,18 @@ const char* dd_version(void);
  * optional group (needed by dd_condition only); lateral input widths are 64/128/256/512 for DD_VARIANT_RES and, for
  * DD_VARIANT_SWIN, 192/384/768/1536 (Swin-L) or 128/216/288/288 (MPViT-small, ..._res_mpvit_HAHI.py:32) -- recognised from numel.
  * Call dd_commit_weights after the last dd_set_weight (and again whenever weights changed, e.g.
- * after an optimizer step): it validates completeness and repacks into the kernels' layouts. */
+ * after an optimizer step): it validates completeness, uploads what arrived as host arrays (the FPN, neck and codec
+ * groups with their eval-mode BatchNorm folded in) and packs every weight image on the device, on `stream`; the images are in
+ * place when it returns. */
 int dd_set_weight(dd_handle_t h, const char* name, const float* data, int64_t numel);
 int dd_commit_weights(dd_handle_t h, void* stream);
 
 /* Same as dd_set_weight for parameters that already live in HBM: `data` is a DEVICE pointer (the nn.Parameter's own storage; borrowed
  * for the call, copied on `stream`).  Replaces the parameter refresh that nn.Module gets for free after optimizer.step() in the
  * reference's training loop (src/main.py:232-241): with this entry point the denoiser's weights go fp32 -> kernel layouts entirely on
- * the device at the next dd_commit_weights (pack kernels on `stream`; no host copy, no host-side packing).  Denoiser group ("model.*")
- * only: the codec and FPN groups are folded with their eval-mode BatchNorm on the host (dd_set_weight) and only run in eval mode.
- * The two routes may be mixed freely; the newest value of every parameter wins.  dd_commit_weights repacks only the groups that
+ * the device at the next dd_commit_weights (the same pack kernels that serve dd_set_weight, minus the upload).  Denoiser group ("model.*")
+ * only: the codec, FPN and neck groups are folded with their eval-mode BatchNorm on the host (dd_set_weight) and only run in eval mode.
+ * The two calls may be mixed freely; the newest value of every parameter wins.  dd_commit_weights repacks only the groups that
  * changed since the last commit. */
 int dd_set_weight_device(dd_handle_t h, const char* name, const float* data, int64_t numel, void* stream);
 
@@ -288,7 +290,8 @@ int dd_get_layer_ms(dd_handle_t h, int layer, double* total_ms, int64_t* launche
  * fp32 NCHW: name in {"y1","y2","y3","y4"} = raw conv outputs before GroupNorm (B,C,h,w).
  * Test hook for locating a failing layer. */
 int dd_debug_fetch(dd_handle_t h, const char* name, float* out, int64_t numel, void* stream);
-/* Test hook: 64-bit FNV-1a digest of every packed denoiser weight buffer in HBM (the two parameter routes must agree bit for bit). */
+/* Test hook: 64-bit FNV-1a digest of every packed denoiser weight buffer in HBM and, once those groups are committed, of the folded FPN and
+ * neck images and biases (host arrays and device tensors must leave the same bytes; tests/golden/weight_digests.json records them). */
 int dd_debug_weights_digest(dd_handle_t h, uint64_t* digest);
 
 #ifdef __cplusplus

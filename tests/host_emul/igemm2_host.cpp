@@ -3,7 +3,7 @@
 // kernels have hundreds of green GPU parity tests; what the GPU cannot show is that they are free of RACES that the hardware's timing happens
 // not to trigger: here a wave runs ahead as far as the workgroup barriers allow, and an LDS-DMA lands either at issue or as late as the
 // s_waitcnt arithmetic permits (dd_gcn.h) -- the results must not depend on any of it.
-#include "dd_kernels.h"
+#include "dd_api_internal.h"
 
 extern "C" {
 
@@ -28,6 +28,25 @@ int emu_conv2(int layer, int ek, const void* in, const void* wpack, const float*
   p.tiles_x = (w + 31) / 32;
   p.tiles_y = (h + g.th - 1) / g.th;
   return dd::launch_conv_igemm2(layer, ek, p, nullptr);
+}
+
+// fp32 W[cout][cin][ks][ks] (transposed: the tensor whose data-gradient convolution is packed) into the swizzled weight image of (layer, element
+// kind) by the library's pack kernel; dst holds pack_weights_bytes of that pair
+int emu_pack(int layer, int ek, const float* src, void* dst, int transposed) {
+  const dd::PackGeom g = dd::conv_pack_geom2(layer, ek);
+  if (g.cout == 0) return (int)hipErrorInvalidValue;
+  return (int)dd::launch_pack_weights(src, dst, g, ek, true, transposed != 0, nullptr);
+}
+
+// The library's own way to a weight image (ddapi::pack_images: every group of dd_commit_weights and the hoisted Swin form go through it) for a
+// tensor of `numel` elements: the status code of the call; on success the image of slot `slot` is copied to `out` (out_bytes = its size, else -1)
+int emu_pack_images(dd_handle_t h, const float* w, long long numel, int layer, int slot, void* out, long long out_bytes) {
+  DevBuf images[NUM_WIMG];
+  const int rc = pack_images(h, w, numel, layer, &slot, 1, images, false, nullptr);
+  if (rc != DD_OK) return rc;
+  if ((long long)images[slot].bytes != out_bytes) return -1;
+  std::memcpy(out, images[slot].p, (size_t)out_bytes);
+  return DD_OK;
 }
 
 }  // extern "C"

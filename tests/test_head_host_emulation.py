@@ -140,7 +140,7 @@ def test_training_step_with_optimizer_refresh_vs_reference_golden(on_host, golde
     assert be.weights_digest() != d0
     fresh = on_host(CPU)
     fresh.load_state_dict({"model." + k: v for k, v in head.model.state_dict().items()}, device_route=False)
-    assert fresh.weights_digest() == be.weights_digest()           # device route == host route on the updated values
+    assert fresh.weights_digest() == be.weights_digest()           # device pointers == host arrays on the updated values
     assert not torch.equal(out2["pred"], out["pred"])
 
 
@@ -284,8 +284,8 @@ def test_the_host_never_blocks_in_steady_state(on_host, lib, monkeypatch):
     """Runtime calls after which the HOST waits for the device (hipDeviceSynchronize / hipStreamSynchronize / hipEventSynchronize, blocking
     hipMemcpy, hipMalloc / hipFree; counted by the emulated runtime): once plans, graphs and workspaces exist, an eval forward of the head
     -- encoder, dd_condition, the loop, decoder, the ddim_loss call -- makes NONE, nor does a training step's backward; the per-step
-    parameter refresh costs 2 by the device route (one device sync before the images are overwritten, one stream sync after) against dozens
-    by the host route (a synchronous upload per packed image)."""
+    parameter refresh costs 2 (one device sync before the images are overwritten, one stream sync after), whether Python hands the parameters
+    over as device pointers or as host arrays: the library uploads the latter at commit and packs both on the device."""
     lib.emu_blocking_calls.restype = ctypes.c_ulong
     sd = synth.make_state_dict(7240)
     sd.update(synth.make_fpn_state_dict(7241))
@@ -317,7 +317,7 @@ def test_the_host_never_blocks_in_steady_state(on_host, lib, monkeypatch):
             opt.zero_grad()
         per_route[route] = (c1 - c0, c2 - c1)                                   # second iteration = steady state
     assert per_route["1"] == (2, 0), per_route
-    assert per_route["0"][1] == 0 and per_route["0"][0] > 20, per_route
+    assert per_route["0"] == (2, 0), per_route
 
 
 def test_training_refuses_to_continue_on_non_finite_gradients(on_host, monkeypatch):

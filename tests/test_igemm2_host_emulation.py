@@ -56,8 +56,9 @@ def act_unlayout(buf, C):
 
 
 def pack_weights(w_oihw, geom, ek):
-    """dd_api.cpp pack_conv_weights (v2, swizzled): [n_tile][cin_chunk][tap_group][tap][n (NT)][k (CK)], zero beyond COUT, the 16-byte piece
-    index of row r = tap * NT + n XORed with (r / (256 / rowbytes)) & (rowbytes / 16 - 1)"""
+    """The packed weight image of the fused kernels, written independently of the library's one packer (pack_weights_kernel, dd_misc.hip; the two
+    are compared byte for byte below): [n_tile][cin_chunk][tap_group][tap][n (NT)][k (CK)], zero beyond COUT, the 16-byte piece index of row
+    r = tap * NT + n XORed with (r / (256 / rowbytes)) & (rowbytes / 16 - 1)"""
     cin, cout, cout_pad, ck, tg, nt, th, ks = geom
     e = esz(ek)
     wp = np.zeros((cout_pad, cin, ks * ks), np.float32)
@@ -247,8 +248,34 @@ def test_fpn_lateral_layers(emu, layer):
 
 @pytest.mark.parametrize("layer", [20, 21, 22, 23])
 def test_data_gradient_layers(emu, layer):
-    """backward of conv4 .. conv1: the same implicit GEMM on transposed / flipped weights (the transposition is the host's, not tested here)"""
+    """backward of conv4 .. conv1: the same implicit GEMM on transposed / flipped weights (the transposition is the pack kernel's: test_pack_kernel_writes_the_numpy_packers_image)"""
     run_layer(emu, layer, EK_F16, order=1, late=1)
+
+
+@pytest.mark.parametrize("ek", [EK_F32, EK_BF16, EK_F16])
+@pytest.mark.parametrize("layer", [1, 2, 4, 14, 20])
+def test_pack_kernel_writes_the_numpy_packers_image(emu, layer, ek):
+    """dd::launch_pack_weights -- since the host-side packer went, the only code that lays weights out for the kernels -- against pack_weights
+    above, byte for byte: 16-channel input (1), 64 -> 256 (2), cout 16 padded to a tile (4), ks = 1 with 1024 couts (14), a data-gradient layer
+    (20); and with transposed = 1 against pack_weights of the flipped transpose.  Values that round, overflow f16 and fall into its subnormals."""
+    g10 = (ctypes.c_int * 10)()
+    emu.emu_geom2(layer, ek, g10)
+    geom = tuple(g10)[:8]
+    cin, cout, cout_pad, ck, tg, nt, th, ks = geom
+    assert cout > 0 and g10[8] == 1 and g10[9] == 0            # (one plane, nothing stacked: what pack_weights describes)
+    rng = np.random.default_rng(17 * layer + ek)
+    w = rng.standard_normal((cout, cin, ks, ks)).astype(np.float32)
+    w.reshape(-1)[:8] = [0.0, -0.0, 70000.0, -70000.0, 3e-6, -1e-8, 65504.0, 1.0009765625]
+    n_bytes = cout_pad * cin * ks * ks * esz(ek)
+    emu.emu_pack.argtypes = [ctypes.c_int, ctypes.c_int, P, P, ctypes.c_int]
+    for transposed in (0, 1):
+        src = w if not transposed else np.ascontiguousarray(w.transpose(1, 0, 2, 3)[:, :, ::-1, ::-1])     # [cin][cout]: its dgrad convolution is w
+        got = np.full(n_bytes + 64, 0xA5, np.uint8)
+        assert emu.emu_pack(layer, ek, ptr(src), ptr(got), transposed) == 0
+        with np.errstate(over="ignore"):                      # (70000 -> inf in f16 is the point)
+            want = pack_weights(w, geom, ek)
+        assert want.nbytes == n_bytes and (got[n_bytes:] == 0xA5).all()
+        assert np.array_equal(got[:n_bytes], want.view(np.uint8)), (layer, ek, transposed)
 
 
 def test_batch_two_images(emu):

@@ -21,6 +21,7 @@ import diffusiondepth_amd as dda
 from diffusiondepth_amd import synth
 from hostemu_driver import EmuDenoiser, _p, f32
 from hostemu_util import build_library
+import weight_digest_cases as WC
 from oracle import dcn_oracle as DO
 from oracle import ddim_oracle as O
 
@@ -783,17 +784,19 @@ def test_nlspn_guided_affinity_kernel_vs_oracle(lib):
     assert maxabs(offset, ro) < 5e-5 and maxabs(aff, ra) < 2e-5
 
 
-# ---- parameter routes: host packer (dd_set_weight) vs pack kernels (dd_set_weight_device) -------------------------------------------------------
+# ---- parameter intake: host arrays (dd_set_weight) and device tensors (dd_set_weight_device), one packer behind both ----------------------------
 @pytest.mark.parametrize("variant", ["res", "swin"])
 def test_device_route_packs_every_weight_buffer_bit_for_bit(lib, variant):
-    """dd_set_weight_device + dd_commit_weights (pack_weights_kernel / transpose_flip_kernel / D2D copies: what a training loop uses
-    after optimizer.step()) must leave exactly the bytes in HBM that the host packer leaves: v1 / v2 / data-gradient images of every
-    convolution in all three element kinds, padded biases, GroupNorm affines, embedding, the per-tap E[t] table."""
+    """dd_set_weight_device + dd_commit_weights (what a training loop uses after optimizer.step()) and dd_set_weight + dd_commit_weights (a
+    host array uploaded as fp32 at commit) must leave the same bytes in HBM -- forward / data-gradient images of every convolution in all element
+    kinds, padded biases, GroupNorm affines, embedding, the per-tap E[t] table -- and those are the bytes the host-side packer left before it was
+    removed: the digests recorded from it (tests/golden/weight_digests.json) keep this from being a comparison of one function with itself."""
     sd = synth.make_state_dict(7301, variant)
+    rec = WC.recorded("hostemu")
     host, dev, mixed = EmuDenoiser(lib, variant), EmuDenoiser(lib, variant), EmuDenoiser(lib, variant)
     host.load_state_dict(sd)
     dev.load_state_dict(sd, device_route=True)
-    assert dev.weights_digest() == host.weights_digest()
+    assert dev.weights_digest() == host.weights_digest() == rec[variant]
     # mixed update of one group: the newest value of every parameter wins, whichever route it took
     sd2 = synth.make_state_dict(7302, variant)
     mixed.load_state_dict(sd2, device_route=True)                                      # everything (other values) on the device
@@ -812,6 +815,7 @@ def test_device_route_packs_every_weight_buffer_bit_for_bit(lib, variant):
     fresh = EmuDenoiser(lib, variant)
     fresh.load_state_dict({**sd, **upd})
     assert dev.weights_digest() == fresh.weights_digest() != host.weights_digest()
+    assert fresh.weights_digest() == rec[variant + "_updated"]
     # wrong group / size / name fail loudly
     a = f32(sd["depth_transform.conv_inv_transform.0.bias"])
     with pytest.raises(RuntimeError, match="not a denoiser parameter"):
@@ -822,6 +826,39 @@ def test_device_route_packs_every_weight_buffer_bit_for_bit(lib, variant):
         dev.ck(lib.dd_set_weight_device(dev.h, b"model.nope", _p(a), a.size, None), "x")
     for e in (host, dev, mixed, fresh):
         e.close()
+
+
+@pytest.mark.parametrize("case", [pytest.param(n, marks=full_only if big else ()) for n, (_, big) in WC.CASES.items() if "_fpn" in n or "_neck" in n])
+def test_folded_fpn_and_neck_images_are_the_recorded_host_packers(lib, case):
+    """The condition FPN's and the HAHI neck's images (BatchNorm folded on the host, packed by the pack kernel since the host-side packer went)
+    and folded biases, digested with the denoiser's: equal to what that packer left (tests/golden/weight_digests.json).  Res pyramid always; the
+    Swin-L and MPViT-small pyramids (216 channels carried as 224, the fusion convolutions' shifted input channels) and their necks under
+    DD_EMU_FULL=1."""
+    be = EmuDenoiser(lib, WC.CASES[case][0])
+    be.load_state_dict(WC.state_dict(case))
+    assert be.weights_digest() == WC.recorded("hostemu")[case]
+    be.close()
+
+
+def test_pack_helper_refuses_a_tensor_of_another_size_than_the_kernels_geometry(lib):
+    """ddapi::pack_images (every weight image of the library is made by it) takes the tensor's element count: the pack kernel indexes its source by
+    cout x cin x ks x ks of the kernel's geometry, so another count must fail the call with DD_ERR_INVALID_ARG before anything is read -- driven
+    through the harness hook emu_pack_images on a sound handle."""
+    be = EmuDenoiser(lib, "res")
+    lib.emu_pack_images.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]
+    lib.emu_pack.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    w = np.random.RandomState(3).standard_normal(256 * 64 * 9).astype(np.float32)             # conv2 (kernel id 2): 64 -> 256, 3x3
+    n_bytes = w.size * 2
+    out, direct = np.full(n_bytes, 0xA5, np.uint8), np.zeros(n_bytes, np.uint8)
+    assert lib.emu_pack_images(be.h, _p(w), w.size, 2, 2, _p(out), n_bytes) == 0               # slot 2 = f16
+    assert lib.emu_pack(2, 2, _p(w), _p(direct), 0) == 0 and np.array_equal(out, direct)
+    for wrong in (w.size - 1, w.size + 1, w.size // 9, 256 * 256 * 9):
+        out[:] = 0xA5
+        # (the buffer handed over really holds `wrong` elements: a library that packed anyway would read inside it or, for the larger ones, show below)
+        buf = np.zeros(max(wrong, w.size), np.float32)
+        assert lib.emu_pack_images(be.h, _p(buf), wrong, 2, 2, _p(out), n_bytes) == 1          # DD_ERR_INVALID_ARG
+        assert "the tensor has %d" % wrong in lib.dd_last_error(be.h).decode() and (out == 0xA5).all()
+    be.close()
 
 
 def test_device_route_results_and_commit_of_changed_groups_only(lib):

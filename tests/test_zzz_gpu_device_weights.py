@@ -1,13 +1,15 @@
-"""GPU (`-m gpu`), last in collection order on purpose: the device route of the denoiser parameters (dd_set_weight_device -> pack kernels of
-dd_misc.hip; include/ddepth.h).  It is what keeps a training iteration's parameter refresh in HBM after optimizer.step(); it has been
-validated bit for bit against the host packer under host emulation (tests/test_library_host_emulation.py); this file passed on an
-MI355X in round 2 (profiles/history/r02_run10_pytest_gpu.txt), since when the route is the default (DDEPTH_DEVICE_WEIGHTS=1)."""
+"""GPU (`-m gpu`), last in collection order on purpose: the two ways parameters reach the library -- host arrays (dd_set_weight, uploaded as
+fp32 at commit) and device tensors (dd_set_weight_device: what keeps a training iteration's parameter refresh in HBM after optimizer.step(), the
+default since round 2, DDEPTH_DEVICE_WEIGHTS=1) -- and the one packer behind both, the pack kernels of dd_misc.hip.  The host-side packer that
+used to serve the first way is gone; the digests it left on an MI355X are recorded in tests/golden/weight_digests.json (key "mi355x") and every
+comparison here is tied to them."""
 import numpy as np
 import pytest
 import torch
 
 import diffusiondepth_amd as dda
 from diffusiondepth_amd import synth
+import weight_digest_cases as WC
 
 pytestmark = pytest.mark.gpu
 
@@ -22,13 +24,23 @@ def test_pack_kernels_leave_the_host_packers_bytes_in_hbm(variant):
     host, dev = dda.HipDenoiser(variant=variant), dda.HipDenoiser(variant=variant)
     host.load_state_dict(sd, device_route=False)
     dev.load_state_dict(_cuda_sd(sd), device_route=True)
-    assert dev.weights_digest() == host.weights_digest()
+    assert dev.weights_digest() == host.weights_digest() == WC.recorded("mi355x")[variant]
     # a second, different set through the device route (buffers reused), against a fresh host load
     upd = {k: (v * 1.25 + 0.01).astype(np.float32) for k, v in sd.items() if k.startswith("model.")}
     dev.load_state_dict(_cuda_sd(upd), device_route=True)
     fresh = dda.HipDenoiser(variant=variant)
     fresh.load_state_dict({**sd, **upd}, device_route=False)
     assert dev.weights_digest() == fresh.weights_digest() != host.weights_digest()
+    assert fresh.weights_digest() == WC.recorded("mi355x")[variant + "_updated"]
+
+
+@pytest.mark.parametrize("case", [n for n in WC.CASES if "_fpn" in n or "_neck" in n])
+def test_folded_fpn_and_neck_images_are_the_recorded_host_packers(case):
+    """Condition FPN and HAHI neck of every pyramid (BatchNorm folded on the host, images by the pack kernel): the digest over the denoiser's, the
+    FPN's and the neck's buffers equals the one recorded from the host-side packer."""
+    be = dda.HipDenoiser(variant=WC.CASES[case][0])
+    be.load_state_dict(WC.state_dict(case), device_route=False)
+    assert be.weights_digest() == WC.recorded("mi355x")[case]
 
 
 def test_training_refresh_through_the_module_tree_stays_on_the_device(monkeypatch):
