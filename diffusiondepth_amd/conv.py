@@ -18,6 +18,13 @@ module's precision is "bf16", "f16" or "f16x3", and the channel counts are suppo
 with ``channels="any"`` (``conv_backend="hip+all"``), multiples of 8 in 8..2048 through dd_convx_*.  Everything else -- CPU
 tensors, the "fp32" / "f16r" / "naive_fp32" precisions, other dtypes or layouts -- calls the torch forward the module inherits.  It is never a
 fallback after an error, nothing is copied or converted silently, and there is no CPU library path.
+
+Scale of the incoming gradient (opt-in, ``grad_autoscale``).  The kernels round ``grad_y`` to f16 as it arrives; a training step's gradients are
+about 3e-7 (the loss is a mean over millions of pixels), below f16's normal range.  With ``grad_autoscale=True`` the backward of "f16" / "f16x3"
+multiplies ``grad_y`` by a power of two taken from its largest finite magnitude on the device, and the result by the inverse
+(include/ddepth_conv_scaled.h): nothing else changes, and "bf16" is left as it is.  Off by default -- today's calls and today's bits:
+
+    convert_hip_conv(head.conv_lateral, "f16x3", grad_autoscale=True)      # or: conv_grad_autoscale=True / DDEPTH_CONV_GRAD_AUTOSCALE=1
 """
 from __future__ import annotations
 
@@ -38,6 +45,9 @@ ABI_SYMBOLS = ["dd_conv_last_error", "dd_conv_supported", "dd_conv_workspace_byt
                "dd_conv1x1_forward", "dd_conv1x1_backward_data", "dd_conv1x1_backward_weight",
                "dd_convx_supported", "dd_convx_workspace_bytes", "dd_convx_forward", "dd_convx_backward_data", "dd_convx_backward_weight"]
 
+# every symbol include/ddepth_conv_scaled.h declares (tests/test_conv_scaled_cpu.py); bound on first use, so ABI_SYMBOLS and _lib() stay what they were
+ABI_SYMBOLS_SCALED = ["dd_conv_grad_scale", "dd_convx_backward_data_scaled", "dd_convx_backward_weight_scaled"]
+
 OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
 _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
@@ -49,7 +59,10 @@ _ENTRY_ANY = ("dd_convx_forward", "dd_convx_backward_data", "dd_convx_backward_w
 # runs a block-64 shape through the same kernels)
 CHANNELS = ("block64", "any")
 
+_ENTRY_SCALED = (None, "dd_convx_backward_data_scaled", "dd_convx_backward_weight_scaled")      # (op, ..., scale, ...): always the extended range
+
 _bound = None
+_bound_scaled = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
 
@@ -74,6 +87,19 @@ def _lib():
             f.restype, f.argtypes = c_int, [c_int] + [c_vp] * 4 + [c_int] * 6 + [c_vp]
         _bound = lib
     return _bound
+
+
+def _lib_scaled():
+    global _bound_scaled
+    if _bound_scaled is None:
+        lib = _lib()
+        c_int, c_vp = ctypes.c_int, ctypes.c_void_p
+        lib.dd_conv_grad_scale.restype, lib.dd_conv_grad_scale.argtypes = c_int, [c_vp, ctypes.c_int64, c_int, c_vp, c_vp]
+        for n in _ENTRY_SCALED[1:]:
+            f = getattr(lib, n)
+            f.restype, f.argtypes = c_int, [c_int] + [c_vp] * 5 + [c_int] * 6 + [c_vp]
+        _bound_scaled = lib
+    return _bound_scaled
 
 
 def _ck(rc, what):
@@ -142,9 +168,15 @@ def _geometry(op: int, x: torch.Tensor, w: torch.Tensor):
     return B, cin, cout, H, W
 
 
-def _call(op, which, a, b, out, dims, prec, channels):
+def _call(op, which, a, b, out, dims, prec, channels, scale=None):
     B, cin, cout, H, W = dims
     with torch.cuda.device(a.device):
+        if scale is not None:      # dd_convx_*_scaled: the extended contract (a superset) and its workspace, whichever contract the module has
+            ws = workspace_for(a, op, B, cin, cout, H, W, prec, "any")
+            name = _ENTRY_SCALED[which]
+            _ck(getattr(_lib_scaled(), name)(op, a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), scale.data_ptr(), B, cin, cout, H, W,
+                                             prec, _stream(a)), name)
+            return out
         ws = workspace_for(a, op, B, cin, cout, H, W, prec, channels)
         args = (a.data_ptr(), b.data_ptr(), out.data_ptr(), ws.data_ptr(), B, cin, cout, H, W, prec, _stream(a))
         if _any(channels):
@@ -167,25 +199,47 @@ def conv_forward(op: int, x: torch.Tensor, w: torch.Tensor, prec: int, channels=
     return _call(op, 0, x, w, torch.empty((B, cout, s * H, s * W), dtype=torch.float32, device=x.device), dims, prec, channels)
 
 
-def conv_backward_data(op: int, grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int, channels="block64") -> torch.Tensor:
+def _check_scale(scale, like: torch.Tensor):
+    if scale is not None and not (scale.is_cuda and scale.device == like.device and scale.dtype == torch.float32 and scale.is_contiguous()
+                                  and scale.numel() >= 4):
+        raise RuntimeError("scale must be the 4-float device tensor grad_scale returns, on grad_y's device")
+
+
+def grad_scale(grad_y: torch.Tensor, prec: int) -> torch.Tensor:
+    """dd_conv_grad_scale: a fresh 4-float device tensor {s, 1 / s, bits of amax, 0} with s = 2^(14 - floor(log2 amax)) for the largest finite
+    |grad_y| (include/ddepth_conv_scaled.h; "bf16": {1, 1}, no pass over grad_y).  From the caching allocator; nothing synchronises the host.
+    Compute it once per backward and pass it to both ``conv_backward_data`` and ``conv_backward_weight``."""
+    _check_native(grad_y, "grad_y")
+    scale = torch.empty(4, dtype=torch.float32, device=grad_y.device)
+    with torch.cuda.device(grad_y.device):
+        _ck(_lib_scaled().dd_conv_grad_scale(grad_y.data_ptr(), grad_y.numel(), int(prec), scale.data_ptr(), _stream(grad_y)), "dd_conv_grad_scale")
+    return scale
+
+
+def conv_backward_data(op: int, grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int, channels="block64", *, scale=None) -> torch.Tensor:
+    """``scale`` (a ``grad_scale`` tensor; None: none): run dd_convx_backward_data_scaled, whichever ``channels`` says."""
     _any(channels)      # (a wrong value is an error before anything else)
     _check_native(grad_y, "grad_y")
     _check_native(w, "weight")
+    _check_scale(scale, grad_y)
     grad_x = torch.empty(tuple(x_shape), dtype=torch.float32, device=grad_y.device)
-    return _call(op, 1, grad_y, w, grad_x, _geometry(op, grad_x, w), prec, channels)
+    return _call(op, 1, grad_y, w, grad_x, _geometry(op, grad_x, w), prec, channels, scale)
 
 
-def conv_backward_weight(op: int, x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int, channels="block64") -> torch.Tensor:
+def conv_backward_weight(op: int, x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int, channels="block64", *, scale=None) -> torch.Tensor:
+    """``scale``: as in ``conv_backward_data`` (dd_convx_backward_weight_scaled)."""
     _any(channels)      # (a wrong value is an error before anything else)
     _check_native(x, "x")
     _check_native(grad_y, "grad_y")
+    _check_scale(scale, grad_y)
     grad_w = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
-    return _call(op, 2, x, grad_y, grad_w, _geometry(op, x, grad_w), prec, channels)
+    return _call(op, 2, x, grad_y, grad_w, _geometry(op, x, grad_w), prec, channels, scale)
 
 
-def _forward(ctx, op, x, weight, prec, channels):
+def _forward(ctx, op, x, weight, prec, channels, grad_autoscale=False):
     ctx.save_for_backward(x, weight)
     ctx.conf = (int(op), int(prec), channels)
+    ctx.grad_autoscale = bool(grad_autoscale)
     # (positional, and the default contract with exactly the arguments it always had: callers wrap these three functions)
     extra = (channels,) if _any(channels) else ()
     return conv_forward(op, x, weight.detach(), int(prec), *extra)
@@ -197,23 +251,25 @@ def _backward(ctx, grad_y):
     extra = (channels,) if _any(channels) else ()
     need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
     if not (need_x or need_w):
-        return None, None, None, None
+        return None, None, None, None, None
     gy = grad_y.detach()
     if gy.dtype != torch.float32 or not gy.is_contiguous():
         gy = gy.float().contiguous()
-    gx = conv_backward_data(op, gy, weight.detach(), x.shape, prec, *extra) if need_x else None      # not for a detached input
-    gw = conv_backward_weight(op, x, gy, weight.shape, prec, *extra) if need_w else None             # not for a frozen weight
-    return gx, gw, None, None
+    # (without the rescale: exactly the calls there always were)
+    scaled = {"scale": grad_scale(gy, prec)} if ctx.grad_autoscale else {}      # once: grad_y is reduced once for both directions
+    gx = conv_backward_data(op, gy, weight.detach(), x.shape, prec, *extra, **scaled) if need_x else None      # not for a detached input
+    gw = conv_backward_weight(op, x, gy, weight.shape, prec, *extra, **scaled) if need_w else None             # not for a frozen weight
+    return gx, gw, None, None, None
 
 
 class Conv3x3Function(Function):
     """(x, weight, dd_precision[, channels]) -> F.conv2d(x, weight, None, 1, 1) over the three dd_conv3x3_* calls (``channels="any"``: over
     dd_convx_*; the choice travels in ``ctx.conf``).  Kept for the backward: x and weight.  A gradient ``ctx.needs_input_grad`` does not ask for
-    is not computed.  Nothing synchronises the host."""
+    is not computed.  ``grad_autoscale``: the backward rescales grad_y by a power of two (module docstring).  Nothing synchronises the host."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec, channels="block64"):
-        return _forward(ctx, OP_CONV3X3, x, weight, prec, channels)
+    def forward(ctx, x, weight, prec, channels="block64", grad_autoscale=False):
+        return _forward(ctx, OP_CONV3X3, x, weight, prec, channels, grad_autoscale)
 
     @staticmethod
     @once_differentiable
@@ -225,8 +281,8 @@ class Conv1x1Function(Function):
     """(x, weight, dd_precision) -> F.conv2d(x, weight) with a [Cout, Cin, 1, 1] weight over the three dd_conv1x1_* calls; as Conv3x3Function."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec, channels="block64"):
-        return _forward(ctx, OP_CONV1X1, x, weight, prec, channels)
+    def forward(ctx, x, weight, prec, channels="block64", grad_autoscale=False):
+        return _forward(ctx, OP_CONV1X1, x, weight, prec, channels, grad_autoscale)
 
     @staticmethod
     @once_differentiable
@@ -238,8 +294,8 @@ class ConvTranspose2x2Function(Function):
     """(x, weight, dd_precision) -> F.conv_transpose2d(x, weight, None, 2) over the three dd_deconv2x2_* calls; as Conv3x3Function."""
 
     @staticmethod
-    def forward(ctx, x, weight, prec, channels="block64"):
-        return _forward(ctx, OP_DECONV2X2, x, weight, prec, channels)
+    def forward(ctx, x, weight, prec, channels="block64", grad_autoscale=False):
+        return _forward(ctx, OP_DECONV2X2, x, weight, prec, channels, grad_autoscale)
 
     @staticmethod
     @once_differentiable
@@ -280,6 +336,15 @@ def _channels_repr(channels) -> str:
     return "" if channels == "block64" else f", channels={channels}"
 
 
+def _autoscale_repr(on) -> str:
+    return ", grad_autoscale=True" if on else ""
+
+
+def _apply(fn, x, weight, prec, channels, grad_autoscale):
+    # (off: the call with exactly the arguments it always had)
+    return fn.apply(x, weight, prec, channels, True) if grad_autoscale else fn.apply(x, weight, prec, channels)
+
+
 class HipConv2d(nn.Conv2d):
     """``nn.Conv2d(cin, cout, 3, 1, 1, bias=False)`` or ``nn.Conv2d(cin, cout, 1, bias=False)`` (same parameter, same state-dict key) whose
     forward and backward on a HIP device run in csrc/dd_conv.hip on ``precision`` operands ("bf16", "f16", "f16x3"); the operator (3x3 or
@@ -287,13 +352,14 @@ class HipConv2d(nn.Conv2d):
     docstring) runs the inherited torch forward."""
 
     channels = "block64"      # the channel contract (CHANNELS); a class attribute, so modules made before it existed behave as they did
+    grad_autoscale = False    # rescale grad_y by a power of two in the "f16" / "f16x3" backward (module docstring); likewise a class attribute
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias=bias, **kwargs)
         self.precision = precision
 
     def extra_repr(self):
-        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels)
+        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels) + _autoscale_repr(self.grad_autoscale)
 
     def _native(self, x) -> Optional[int]:
         """The dd_conv_op this call runs in the library, or None for the torch forward."""
@@ -307,20 +373,22 @@ class HipConv2d(nn.Conv2d):
         op = self._native(x)
         if op is None:
             return super().forward(x)
-        return (Conv3x3Function if op == OP_CONV3X3 else Conv1x1Function).apply(x, self.weight, precision_id(self.precision), self.channels)
+        return _apply(Conv3x3Function if op == OP_CONV3X3 else Conv1x1Function, x, self.weight, precision_id(self.precision), self.channels,
+                      self.grad_autoscale)
 
 
 class HipConvTranspose2d(nn.ConvTranspose2d):
     """``nn.ConvTranspose2d(cin, cout, 2, 2, bias=False)``; as HipConv2d."""
 
     channels = "block64"
+    grad_autoscale = False
 
     def __init__(self, in_channels, out_channels, kernel_size=2, stride=2, padding=0, output_padding=0, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, output_padding, bias=bias, **kwargs)
         self.precision = precision
 
     def extra_repr(self):
-        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels)
+        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels) + _autoscale_repr(self.grad_autoscale)
 
     def _native(self, x, output_size) -> bool:
         return bool(output_size is None and _is_deconv2x2(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels
@@ -329,7 +397,7 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
     def forward(self, x, output_size=None):
         if not self._native(x, output_size):
             return super().forward(x, output_size)
-        return ConvTranspose2x2Function.apply(x, self.weight, precision_id(self.precision), self.channels)
+        return _apply(ConvTranspose2x2Function, x, self.weight, precision_id(self.precision), self.channels, self.grad_autoscale)
 
 
 def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64") -> bool:
@@ -346,7 +414,7 @@ def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64
     return False
 
 
-def _from_conv(m, precision, channels="block64"):
+def _from_conv(m, precision, channels="block64", grad_autoscale=False):
     cls = HipConvTranspose2d if isinstance(m, nn.ConvTranspose2d) else HipConv2d
     out = cls.__new__(cls)
     nn.Module.__init__(out)
@@ -356,19 +424,22 @@ def _from_conv(m, precision, channels="block64"):
     out.precision = precision
     if channels != "block64":      # (the default stays the class attribute)
         out.channels = channels
+    if grad_autoscale:
+        out.grad_autoscale = True
     return out
 
 
-def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False, channels="block64") -> nn.Module:
+def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False, channels="block64", grad_autoscale: bool = False) -> nn.Module:
     """Every eligible convolution of ``module`` (see ``eligible``) becomes a ``HipConv2d`` / ``HipConvTranspose2d`` holding the SAME parameter
     tensor under the same name: state-dict keys and the indices inside an ``nn.Sequential`` do not change.  With a precision the library does
     not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced.  A 1x1
     convolution is replaced only with ``pointwise=True`` (the HAHI neck); the default leaves every 1x1 an ``nn.Conv2d``.  ``channels="any"``
     takes every multiple of 8 in 8..2048 (MPViT's 216 / 288, Swin-L's 2048 -> 1536) and marks the new modules with it; the default keeps
-    the block-64 contract, multiples of 64 in 64..1536."""
-    out = _from_conv(module, precision, channels) if eligible(module, precision, pointwise, channels) else module
+    the block-64 contract, multiples of 64 in 64..1536.  ``grad_autoscale=True`` marks the new modules so that their "f16" / "f16x3" backward
+    rescales the incoming gradient by a power of two (module docstring); the default leaves the backward as it is."""
+    out = _from_conv(module, precision, channels, grad_autoscale) if eligible(module, precision, pointwise, channels) else module
     for name, child in list(module.named_children()):
-        new = convert_hip_conv(child, precision, pointwise, channels)
+        new = convert_hip_conv(child, precision, pointwise, channels, grad_autoscale)
         if new is not child:
             setattr(out, name, new)
     return out
@@ -382,3 +453,14 @@ def resolve_conv_backend(conv_backend: Optional[str] = None) -> str:
     if choice not in ("torch", "hip", "hip+neck", "hip+all"):
         raise ValueError(f"conv_backend must be 'torch', 'hip', 'hip+neck' or 'hip+all' (got {choice!r})")
     return choice
+
+
+def resolve_conv_grad_autoscale(conv_grad_autoscale: Optional[bool] = None) -> bool:
+    """The head keyword ``conv_grad_autoscale`` / the environment variable DDEPTH_CONV_GRAD_AUTOSCALE ("1" is on; "0", empty or absent is off, the
+    default): whether the converted convolutions rescale the incoming gradient in the "f16" / "f16x3" backward."""
+    if conv_grad_autoscale is not None:
+        return bool(conv_grad_autoscale)
+    choice = os.environ.get("DDEPTH_CONV_GRAD_AUTOSCALE") or "0"
+    if choice not in ("0", "1"):
+        raise ValueError(f"DDEPTH_CONV_GRAD_AUTOSCALE must be '0' or '1' (got {choice!r})")
+    return choice == "1"

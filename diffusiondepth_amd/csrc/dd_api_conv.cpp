@@ -1,6 +1,8 @@
-// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h: argument checks and the launch sequence; the kernels are in dd_conv.hip.
+// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h and include/ddepth_conv_scaled.h: argument checks and the launch sequence; the kernels
+// are in dd_conv.hip.
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_conv.h"
+#include "../../include/ddepth_conv_scaled.h"
 #include "dd_conv.h"
 #include "dd_status.h"
 
@@ -55,21 +57,24 @@ int workspace_bytes(ChannelContract contract, int op, int B, int Cin, int Cout, 
   return DD_OK;
 }
 
+// scale: NULL for the functions of ddepth_conv.h, the device pair of dd_conv_grad_scale for those of ddepth_conv_scaled.h (`scaled`)
 int run_conv(ChannelContract contract, int op, int dir, const float* in, const float* w, float* out, void* ws, int B, int Cin, int Cout, int H,
-             int W, int precision, void* stream) {
+             int W, int precision, void* stream, bool scaled = false, const float* scale = nullptr) {
   int prec = 0;
   if (int rc = check(contract, op, B, Cin, Cout, H, W, precision, &prec)) return rc;
   if (int rc = ddstatus::check_ptrs(g_conv_err, in, w, out, ws)) return rc;
-  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv(op, dir, in, w, out, ws, B, Cin, Cout, H, W, prec, (hipStream_t)stream));
+  if (scaled && !scale) return g_conv_err.fail(DD_ERR_INVALID_ARG, "scale is NULL");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv(op, dir, in, w, out, ws, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
   return DD_OK;
 }
 
 int run_wgrad(ChannelContract contract, int op, const float* x, const float* grad_y, float* grad_w, void* ws, int B, int Cin, int Cout, int H,
-              int W, int precision, void* stream) {
+              int W, int precision, void* stream, bool scaled = false, const float* scale = nullptr) {
   int prec = 0;
   if (int rc = check(contract, op, B, Cin, Cout, H, W, precision, &prec)) return rc;
   if (int rc = ddstatus::check_ptrs(g_conv_err, x, grad_y, grad_w, ws)) return rc;
-  DD_STATUS_HIP(g_conv_err, ddconv::launch_wgrad(op, x, grad_y, grad_w, ws, B, Cin, Cout, H, W, prec, (hipStream_t)stream));
+  if (scaled && !scale) return g_conv_err.fail(DD_ERR_INVALID_ARG, "scale is NULL");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_wgrad(op, x, grad_y, grad_w, ws, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
   return DD_OK;
 }
 
@@ -150,6 +155,28 @@ int dd_convx_backward_data(int op, const float* grad_y, const float* w, float* g
 int dd_convx_backward_weight(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
                              int precision, void* stream) {
   return run_wgrad(kChannelsExtended, op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, precision, stream);
+}
+
+// ---- include/ddepth_conv_scaled.h: the two gradients on grad_y rescaled by a power of two ------------------------------------------------------
+int dd_conv_grad_scale(const float* grad_y, int64_t n, int precision, float* scale, void* stream) {
+  const int prec = kernel_prec(precision);
+  if (prec < 0)
+    return g_conv_err.fail(DD_ERR_UNSUPPORTED, "precision %d is unsupported: this operator runs DD_PREC_BF16, DD_PREC_F16 and DD_PREC_F16X3", precision);
+  if (!scale) return g_conv_err.fail(DD_ERR_INVALID_ARG, "scale is NULL");
+  if (n < 0 || (n > 0 && !grad_y)) return g_conv_err.fail(DD_ERR_INVALID_ARG, "grad_y is NULL or n = %lld is negative", (long long)n);
+  if ((const void*)grad_y == (const void*)scale) return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_grad_scale(grad_y, n, prec, ddconv::kGradAmaxExp, scale, (hipStream_t)stream));
+  return DD_OK;
+}
+
+int dd_convx_backward_data_scaled(int op, const float* grad_y, const float* w, float* grad_x, void* workspace, const float* scale, int B, int Cin,
+                                  int Cout, int H, int W, int precision, void* stream) {
+  return run_conv(kChannelsExtended, op, 1, grad_y, w, grad_x, workspace, B, Cin, Cout, H, W, precision, stream, true, scale);
+}
+
+int dd_convx_backward_weight_scaled(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, const float* scale, int B, int Cin,
+                                    int Cout, int H, int W, int precision, void* stream) {
+  return run_wgrad(kChannelsExtended, op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, precision, stream, true, scale);
 }
 
 }  // extern "C"

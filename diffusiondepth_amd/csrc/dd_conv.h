@@ -47,9 +47,16 @@ size_t packed_halfs(int op, int dir, int Cin, int Cout);
 size_t workspace_bytes(int op, int B, int Cin, int Cout, int H, int W, int prec);
 
 // dir: 0 forward, 1 data gradient.  `in` / `out` are x / y (forward) or grad_y / grad_x (data gradient); H, W = input size of the forward.
+// scale (include/ddepth_conv_scaled.h; NULL: none): the device pair {s, 1 / s} of launch_grad_scale.  With it the two gradients of the f16 modes
+// run the scaled twins of their kernels -- grad_y times s before it is rounded, the result times 1 / s; kBf16 and the forward ignore it.
 hipError_t launch_conv(int op, int dir, const float* in, const float* w, float* out, void* workspace, int B, int Cin, int Cout, int H,
-                       int W, int prec, hipStream_t st);
+                       int W, int prec, hipStream_t st, const float* scale = nullptr);
 hipError_t launch_wgrad(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, int B, int Cin, int Cout, int H, int W,
-                        int prec, hipStream_t st);
+                        int prec, hipStream_t st, const float* scale = nullptr);
+
+// scale[0..3] = {s, 1 / s, bits of amax, 0} with amax the largest finite |grad_y[i]| and s = 2^(amax_exp - floor(log2 amax)) (shift within +-126;
+// amax == 0: s = 1): a memset, one reduction pass (integer atomicMax: order-independent) and a single-thread kernel.  kPrecBf16: {1, 1}, no pass.
+constexpr int kGradAmaxExp = 14;      // s * amax < 2^15 <= 65504, the largest f16: one GEMM accumulates in fp32, nothing behind it can overflow
+hipError_t launch_grad_scale(const float* grad_y, int64_t n, int prec, int amax_exp, float* scale, hipStream_t st);
 
 }  // namespace ddconv

@@ -1,0 +1,419 @@
+// dd_conv_kernels.h -- the GEMM kernels of csrc/dd_conv.hip, written ONCE and included there TWICE: with DD_CONV_SCALED 0 it defines the kernels of
+// include/ddepth_conv.h (dd_conv_igemm_kernel, dd_conv_wgrad_kernel, dd_conv1x1_gemm_kernel, dd_conv1x1_wgrad_kernel, dd_conv_wgrad_reduce_kernel), with
+// DD_CONV_SCALED 1 their twins *_scaled_kernel of include/ddepth_conv_scaled.h, which take the device pair scale = {s, 1 / s} as one more (last)
+// argument, multiply every loaded value of grad_y by s before it is rounded to its 16-bit operand, and undo it with 1 / s where the result is stored:
+//   dd_conv_igemm / dd_conv1x1_gemm   `in` is grad_y (the twins are launched for the data gradients only); the accumulators times 1 / s in the epilogue
+//   dd_conv_wgrad                     grad_y is P for the 3x3 (S == 1) and Q for the transpose convolution (S == 2); the partials stay scaled
+//   dd_conv1x1_wgrad                  grad_y is Pm; the partials stay scaled
+//   dd_conv_wgrad_reduce              writes sum * 1 / s
+// Both factors are powers of two, and the order of every accumulation is untouched.  The preprocessor and not a template argument makes the
+// twins: a kernel's name and argument list are part of what a change may not touch (tools/code_object_diff.py); a template argument would
+// rename every instantiation, and a shared __device__ body inlined into two kernels does not compile to the instruction stream the kernel had.
+// In the unscaled pass every macro below expands to its argument or to nothing: that pass is the text the kernels always had.
+#if DD_CONV_SCALED
+#define DD_CONV_KERNEL(name) name##_scaled_kernel
+#define DD_CONV_SCALE_PARAM , const float* __restrict__ scale      /* the address is the same for every lane: scalar loads */
+#define DD_CONV_GY(is_grad_y, v) ((is_grad_y) ? (v) * scale[0] : (v))
+#define DD_CONV_UNSCALED(v) ((v) * scale[1])
+#else
+#define DD_CONV_KERNEL(name) name##_kernel
+#define DD_CONV_SCALE_PARAM
+#define DD_CONV_GY(is_grad_y, v) (v)
+#define DD_CONV_UNSCALED(v) (v)
+#endif
+
+// ---- forward and data gradient --------------------------------------------------------------------------------------------------------------------
+// in [B][K][Hin][Win], wp [KS * KS][N][K]; grid (tiles, N / 64, B).  The tile grid is Ht x Wt pixels:
+//   !SCATTER: out [B][N][Ht][Wt], pixel (y, x) of the tile grid reads input pixels (y * S - PAD + ky, x * S - PAD + kx)
+//   SCATTER:  out [B][N / 4][2 Ht][2 Wt], GEMM column n = (dy * 2 + dx) * (N / 4) + co goes to pixel (2y + dy, 2x + dx) of plane co
+// RAGGED (K, N multiples of 8, not of the tiles): the weight image is the padded one of the pack kernel, channels >= K are filled as zeros, rows
+// >= N are not stored, and grid y is ceil(N / 64).  The K chunks and their order are those of the block-64 instantiation.
+template <int PREC, int KS, int S, int PAD, int KC, bool SCATTER, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_igemm)(const float* __restrict__ in, const uint16_t* __restrict__ wh,
+                                                                 const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N,
+                                                                 int Hin, int Win, int Ht, int Wt, int tiles_x DD_CONV_SCALE_PARAM) {
+  constexpr int PH = (kTileH - 1) * S + KS, PW = (kTileW - 1) * S + KS, PP = PH * PW;
+  constexpr int PS = KC + 8;      // halfs per patch pixel: a multiple of 8, so every 16-byte read is aligned
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  __shared__ uint16_t patch[NL][PP * PS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x, n0 = blockIdx.y * kTileN, b = blockIdx.z;
+  const int iy0 = ty * kTileH * S - PAD, ix0 = tx * kTileW * S - PAD;
+  const size_t plane = (size_t)Hin * Win;
+  const float* inb = in + (size_t)b * K * plane;
+  const int Kp = RAGGED ? padded(K, KC) : K, Np = RAGGED ? padded(N, kTileN) : N;      // the weight image's row length and rows per tap
+
+  f32x16_t acc[2];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) { acc[0][i] = 0.0f; acc[1][i] = 0.0f; }
+
+  for (int kc = 0; kc < K; kc += KC) {
+    __syncthreads();      // the previous chunk's reads are over
+    // consecutive lanes: consecutive pixels of one plane; kFillBatch loads are issued before the first one is converted
+    for (int base = tid; base < KC * PP; base += kThreads * kFillBatch) {
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, pr = rem / PW, pc = rem - pr * PW;
+        const int iy = iy0 + pr, ix = ix0 + pc;
+        v[j] = 0.0f;
+        if (idx < KC * PP && (!RAGGED || kc + ch < K) && iy >= 0 && iy < Hin && ix >= 0 && ix < Win)
+          v[j] = inb[(size_t)(kc + ch) * plane + (size_t)iy * Win + ix];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
+        if (idx >= KC * PP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(DD_CONV_GY(true, v[j]), hi, lo);
+        patch[0][rem * PS + ch] = hi;
+        if constexpr (PREC == kPrecF16x3) patch[NL - 1][rem * PS + ch] = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ky = 0; ky < KS; ++ky) {
+#pragma unroll
+      for (int kx = 0; kx < KS; ++kx) {
+        const int pp = ((wave * S + ky) * PW + (l32 * S + kx)) * PS + 8 * half;
+        const size_t wrow = ((size_t)(ky * KS + kx) * Np + n0 + l32) * Kp + kc + 8 * half;
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 16) {
+          const uint4 bh = *reinterpret_cast<const uint4*>(&patch[0][pp + kk]);
+          uint4 bl = bh;
+          if constexpr (PREC == kPrecF16x3) bl = *reinterpret_cast<const uint4*>(&patch[NL - 1][pp + kk]);
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            const size_t wo = wrow + (size_t)nb * 32 * Kp + kk;
+            const uint4 ah = *reinterpret_cast<const uint4*>(wh + wo);
+            uint4 al = ah;
+            if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wl + wo);
+            acc[nb] = mma_pair<PREC>(ah, al, bh, bl, acc[nb]);
+          }
+        }
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column (pixel) l % 32, row (output channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
+  const int y = ty * kTileH + wave, x = tx * kTileW + l32;
+  if (y >= Ht || x >= Wt) return;
+#pragma unroll
+  for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int n = n0 + nb * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      if constexpr (RAGGED) {
+        if (n >= N) continue;
+      }
+      if constexpr (SCATTER) {
+        const int cout = N / 4, t4 = n / cout, co = n - t4 * cout;
+        const size_t oy = 2 * (size_t)y + (t4 >> 1), ox = 2 * (size_t)x + (t4 & 1);
+        out[(((size_t)b * cout + co) * (2 * (size_t)Ht) + oy) * (2 * (size_t)Wt) + ox] = acc[nb][r];
+      } else {
+        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = DD_CONV_UNSCALED(acc[nb][r]);
+      }
+    }
+  }
+}
+
+// ---- weight gradient --------------------------------------------------------------------------------------------------------------------------------
+// P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
+//   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
+// part [splits][Cp][Cq][KS * KS]; grid ((Cp / 64) * (Cq / 64), splits).  A pixel tile is RH rows of 32 pixels.
+// RAGGED: grid x is ceil(Cp / 64) * ceil(Cq / 64); channel rows >= Cp / Cq are filled as zeros and not stored (part keeps the real counts).
+template <int PREC, int KS, int S, int PAD, int RH, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_wgrad)(const float* __restrict__ P, const float* __restrict__ Q, float* __restrict__ part,
+                                                                 int Cp, int Cq, int Hp, int Wp, int Hq, int Wq, int tiles_x, int tiles_y,
+                                                                 long long tiles, int tiles_per_split DD_CONV_SCALE_PARAM) {
+  constexpr int T = KS * KS;
+  constexpr int QH = (RH - 1) * S + KS, QW = 31 * S + KS, QP = QH * QW, QCS = wgrad_channel_stride(QP);
+  constexpr int PP = RH * 32, PCS = PP + 8;      // a multiple of 8 halfs: the A operand's 16-byte reads are aligned
+  constexpr int NQ = 7 * S + KS;                 // values of one row of Q that the 8 pixels of a lane touch, all kx together
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  __shared__ uint16_t PL[NL][64 * PCS] __attribute__((aligned(16)));
+  __shared__ uint16_t QL[NL][64 * QCS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int nq = RAGGED ? (Cq + 63) / 64 : Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int wp = wave & 1, wq = wave >> 1;
+  const size_t plane_p = (size_t)Hp * Wp, plane_q = (size_t)Hq * Wq;
+
+  f32x16_t acc[T];
+#pragma unroll
+  for (int t = 0; t < T; ++t)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[t][i] = 0.0f;
+
+  const long long t_begin = (long long)split * tiles_per_split;
+  const long long t_end = t_begin + tiles_per_split < tiles ? t_begin + tiles_per_split : tiles;
+  for (long long t = t_begin; t < t_end; ++t) {
+    const int txi = (int)(t % tiles_x), tyi = (int)((t / tiles_x) % tiles_y), b = (int)(t / ((long long)tiles_x * tiles_y));
+    const int y0 = tyi * RH, x0 = txi * 32;
+    const int qy0 = y0 * S - PAD, qx0 = x0 * S - PAD;
+    __syncthreads();      // the previous tile's reads are over
+    for (int base = tid; base < 64 * PP; base += kThreads * kFillBatch) {      // (kFillBatch loads in flight, as in the implicit GEMM)
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, y = y0 + rem / 32, x = x0 + rem % 32;
+        v[j] = 0.0f;
+        if (idx < 64 * PP && (!RAGGED || p0 + ch < Cp) && y < Hp && x < Wp) v[j] = P[((size_t)b * Cp + p0 + ch) * plane_p + (size_t)y * Wp + x];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
+        if (idx >= 64 * PP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(DD_CONV_GY(S == 1, v[j]), hi, lo);      // (P is grad_y for the 3x3 ...
+        PL[0][ch * PCS + rem] = hi;
+        if constexpr (PREC == kPrecF16x3) PL[NL - 1][ch * PCS + rem] = lo;
+      }
+    }
+    for (int base = tid; base < 64 * QP; base += kThreads * kFillBatch) {
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP, qr = rem / QW, y = qy0 + qr, x = qx0 + (rem - qr * QW);
+        v[j] = 0.0f;
+        if (idx < 64 * QP && (!RAGGED || q0 + ch < Cq) && y >= 0 && y < Hq && x >= 0 && x < Wq) v[j] = Q[((size_t)b * Cq + q0 + ch) * plane_q + (size_t)y * Wq + x];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP;
+        if (idx >= 64 * QP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(DD_CONV_GY(S == 2, v[j]), hi, lo);      // ... and Q for the transpose convolution)
+        QL[0][ch * QCS + rem] = hi;
+        if constexpr (PREC == kPrecF16x3) QL[NL - 1][ch * QCS + rem] = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < RH; ++r) {
+#pragma unroll
+      for (int k16 = 0; k16 < 32; k16 += 16) {
+        const int po = (wp * 32 + l32) * PCS + r * 32 + k16 + 8 * half;
+        const uint4 ah = *reinterpret_cast<const uint4*>(&PL[0][po]);
+        uint4 al = ah;
+        if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(&PL[NL - 1][po]);
+#pragma unroll
+        for (int ky = 0; ky < KS; ++ky) {
+          const int qo = (wq * 32 + l32) * QCS + (r * S + ky) * QW + (k16 + 8 * half) * S;
+          uint16_t qh[NQ], ql[NQ];
+#pragma unroll
+          for (int i = 0; i < NQ; ++i) {
+            qh[i] = QL[0][qo + i];
+            ql[i] = PREC == kPrecF16x3 ? QL[NL - 1][qo + i] : (uint16_t)0;
+          }
+#pragma unroll
+          for (int kx = 0; kx < KS; ++kx) {
+            u16x8_t vh, vl;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+              vh[e] = qh[e * S + kx];
+              vl[e] = ql[e * S + kx];
+            }
+            acc[ky * KS + kx] = mma_pair<PREC>(ah, al, __builtin_bit_cast(uint4, vh), __builtin_bit_cast(uint4, vl), acc[ky * KS + kx]);
+          }
+        }
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column q = l % 32, row p = 8 * (r / 4) + 4 * (l / 32) + r % 4
+  float* dst = part + (size_t)split * Cp * Cq * T;
+  const int q = q0 + wq * 32 + l32;
+#pragma unroll
+  for (int t = 0; t < T; ++t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int p = p0 + wp * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+      if constexpr (RAGGED) {
+        if (p >= Cp || q >= Cq) continue;
+      }
+      dst[((size_t)p * Cq + q) * T + t] = acc[t][r];
+    }
+  }
+}
+
+// ---- 1x1: forward and data gradient ---------------------------------------------------------------------------------------------------------------
+// out[b][n][p] = sum_k wp[n][k] . in[b][k][p] over the FLAT pixels p of a plane (P = H * W): no halo, so a workgroup owns kPwTile consecutive
+// pixels of one plane (wave w the 32 from 32 w on) and 32 * NB output channels; a tile never crosses an image, what lies behind the plane's end
+// is read as zero and not written.  Lane l of the MFMA's pixel-side operand needs channels k + 8 * (l / 32) .. + 7 of pixel l % 32: eight dword
+// loads, each one 32 consecutive floats of one plane (any P, any alignment), converted in registers and already in operand order -- no LDS and no
+// barrier in this kernel.  The weights are the A operand, 16 bytes per lane from the packed image (L1 / L2), as in the implicit GEMM.
+// grid (pixel tiles * N / (32 NB), B): the workgroups of one pixel tile are neighbours in dispatch order, so its re-reads for the other output
+// channels meet the cache.
+// RAGGED (K, N multiples of 8): the weight image is the padded one of the pack kernel (rows of K rounded up to kPwKStep, N rounded up to 64 rows); the
+// pixel-side loads are guarded per 8-channel lane-half group -- K is a multiple of 8, so a tail is always a whole group -- and rows >= N are not
+// stored; N / (32 NB) rounds up.
+template <int PREC, int NB, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv1x1_gemm)(const float* __restrict__ in, const uint16_t* __restrict__ wh,
+                                                                   const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N, int P DD_CONV_SCALE_PARAM) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int Kp = RAGGED ? padded(K, kPwKStep) : K;      // the weight image's row length
+  const int nblocks = RAGGED ? (N + 32 * NB - 1) / (32 * NB) : N / (32 * NB);
+  const int n0 = (int)(blockIdx.x % (unsigned)nblocks) * (32 * NB), b = blockIdx.y;
+  const int pw = (int)(blockIdx.x / (unsigned)nblocks) * kPwTile + wave * 32;      // first pixel of this wave
+  if (pw >= P) return;                                                             // (the whole wave: nothing here waits for it)
+  const int p = pw + l32;
+  const bool live = p < P;
+  const float* src = in + ((size_t)b * K + 8 * half) * (size_t)P + (live ? p : 0);
+  const uint16_t* wrow = wh + (size_t)(n0 + l32) * Kp + 8 * half;
+  const uint16_t* wrow_lo = wl + (size_t)(n0 + l32) * Kp + 8 * half;
+
+  f32x16_t acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[nb][i] = 0.0f;
+
+  for (int kc = 0; kc < K; kc += kPwKStep) {      // (!RAGGED: K is a multiple of 64) sixteen loads in flight, then two MFMA steps
+    float v[2][8];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const bool take = live && (!RAGGED || kc + 16 * s + 8 * half < K);      // this lane's eight channels: all below K, or none
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[s][e] = take ? src[(size_t)(kc + 16 * s + e) * P] : 0.0f;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      u16x8_t vh, vl;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        uint16_t hi, lo;
+        to_operand<PREC>(DD_CONV_GY(true, v[s][e]), hi, lo);
+        vh[e] = hi;
+        vl[e] = lo;
+      }
+      const uint4 bh = __builtin_bit_cast(uint4, vh), bl = __builtin_bit_cast(uint4, vl);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) {
+        const size_t wo = (size_t)nb * 32 * Kp + kc + 16 * s;
+        const uint4 ah = *reinterpret_cast<const uint4*>(wrow + wo);
+        uint4 al = ah;
+        if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wrow_lo + wo);
+        acc[nb] = mma_pair<PREC>(ah, al, bh, bl, acc[nb]);
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column (pixel) l % 32, row (output channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
+  if (!live) return;
+  float* dst = out + ((size_t)b * N + n0 + 4 * half) * (size_t)P + p;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int row = nb * 32 + 8 * (r / 4) + (r % 4);
+      if constexpr (RAGGED) {
+        if (n0 + 4 * half + row >= N) continue;
+      }
+      dst[(size_t)row * P] = DD_CONV_UNSCALED(acc[nb][r]);
+    }
+}
+
+// ---- 1x1: weight gradient -----------------------------------------------------------------------------------------------------------------------------
+// part[split][cp][cq] = sum over the split's pixels of Pm[b][cp][p] . Q[b][cq][p]  (Pm = grad_y, Q = x -> grad_w[co][ci]): the contraction runs over
+// the pixels, contiguous in memory for BOTH operands and shifted for neither.  A workgroup owns 64 x 64 channels and a contiguous range of pixel
+// tiles (a SPLIT, in a fixed order), a tile being kPwTile consecutive pixels of one plane (zero behind its end).  Fill: a wave reads one channel
+// row of the tile with two dword loads per lane, pixels l and 64 + l (coalesced, any alignment), and stores them as ONE dword at slots 2 l,
+// 2 l + 1 of the channel's LDS row -- the MFMA's K runs over the slots, and both operands use the same pixel -> slot map, so the products pair up
+// the same pixels.  Dword stores of consecutive lanes to consecutive addresses, 16-byte operand reads from rows of kPwTile + 8 halfs (the four
+// 16-lane groups of a 16-byte read meet every bank once): no 2-byte scatter or gather anywhere.
+// RAGGED: as in dd_conv_wgrad_kernel -- the grid rounds the channel blocks up, rows >= Cp / Cq are filled as zeros and not stored.
+template <int PREC, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv1x1_wgrad)(const float* __restrict__ Pm, const float* __restrict__ Q, float* __restrict__ part,
+                                                                    int Cp, int Cq, int P, int tiles_per_plane, long long tiles, int tiles_per_split DD_CONV_SCALE_PARAM) {
+  constexpr int RS = kPwTile + 8;      // halfs per channel row
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  constexpr int kFillChannels = kFillBatch / 2;      // channel rows a wave has in flight (two loads each)
+  __shared__ uint16_t PL[NL][64 * RS] __attribute__((aligned(16)));
+  __shared__ uint16_t QL[NL][64 * RS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int nq = RAGGED ? (Cq + 63) / 64 : Cq / 64, p0 = (blockIdx.x / nq) * 64, q0 = (blockIdx.x % nq) * 64, split = blockIdx.y;
+  const int wp = wave & 1, wq = wave >> 1;
+
+  f32x16_t acc;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.0f;
+
+  const long long t_begin = (long long)split * tiles_per_split;
+  const long long t_end = t_begin + tiles_per_split < tiles ? t_begin + tiles_per_split : tiles;
+  for (long long t = t_begin; t < t_end; ++t) {
+    const int b = (int)(t / tiles_per_plane), px = (int)(t % tiles_per_plane) * kPwTile + lane;
+    const bool live0 = px < P, live1 = px + 64 < P;
+    __syncthreads();      // the previous tile's reads are over
+    // rows 0..63 are Pm's channels, 64..127 Q's; wave w fills rows w, w + 4, ...
+    for (int r0 = wave; r0 < 128; r0 += 4 * kFillChannels) {
+      float v[kFillChannels][2];
+#pragma unroll
+      for (int j = 0; j < kFillChannels; ++j) {
+        const int row = r0 + 4 * j;
+        const float* g = row < 64 ? Pm + ((size_t)b * Cp + p0 + row) * (size_t)P : Q + ((size_t)b * Cq + q0 + row - 64) * (size_t)P;
+        bool take0 = live0, take1 = live1;
+        if constexpr (RAGGED) {
+          const bool in_range = row < 64 ? p0 + row < Cp : q0 + row - 64 < Cq;
+          take0 = take0 && in_range;
+          take1 = take1 && in_range;
+        }
+        v[j][0] = take0 ? g[px] : 0.0f;
+        v[j][1] = take1 ? g[px + 64] : 0.0f;
+      }
+#pragma unroll
+      for (int j = 0; j < kFillChannels; ++j) {
+        const int row = r0 + 4 * j;
+        uint16_t h0, l0, h1, l1;
+        to_operand<PREC>(DD_CONV_GY(row < 64, v[j][0]), h0, l0);      // (rows 0..63 are grad_y's; the same choice for a whole wave)
+        to_operand<PREC>(DD_CONV_GY(row < 64, v[j][1]), h1, l1);
+        uint16_t* dh = row < 64 ? &PL[0][row * RS] : &QL[0][(row - 64) * RS];
+        *reinterpret_cast<uint32_t*>(dh + 2 * lane) = (uint32_t)h0 | ((uint32_t)h1 << 16);
+        if constexpr (PREC == kPrecF16x3) {
+          uint16_t* dl = row < 64 ? &PL[NL - 1][row * RS] : &QL[NL - 1][(row - 64) * RS];
+          *reinterpret_cast<uint32_t*>(dl + 2 * lane) = (uint32_t)l0 | ((uint32_t)l1 << 16);
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k16 = 0; k16 < kPwTile; k16 += 16) {
+      const int po = (wp * 32 + l32) * RS + k16 + 8 * half, qo = (wq * 32 + l32) * RS + k16 + 8 * half;
+      const uint4 ah = *reinterpret_cast<const uint4*>(&PL[0][po]);
+      const uint4 bh = *reinterpret_cast<const uint4*>(&QL[0][qo]);
+      uint4 al = ah, bl = bh;
+      if constexpr (PREC == kPrecF16x3) {
+        al = *reinterpret_cast<const uint4*>(&PL[NL - 1][po]);
+        bl = *reinterpret_cast<const uint4*>(&QL[NL - 1][qo]);
+      }
+      acc = mma_pair<PREC>(ah, al, bh, bl, acc);
+    }
+  }
+
+  // accumulator entry r of lane l: column q = l % 32, row p = 8 * (r / 4) + 4 * (l / 32) + r % 4
+  float* dst = part + (size_t)split * Cp * Cq + (size_t)(p0 + wp * 32 + 4 * half) * Cq + q0 + wq * 32 + l32;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    if constexpr (RAGGED) {
+      if (p0 + wp * 32 + 4 * half + 8 * (r / 4) + (r % 4) >= Cp || q0 + wq * 32 + l32 >= Cq) continue;
+    }
+    dst[(size_t)(8 * (r / 4) + (r % 4)) * Cq] = acc[r];
+  }
+}
+
+// grad_w[i] = part[0][i] + part[1][i] + ... in that order (the scaled pass: times 1 / s, the partials being those of the scaled grad_y)
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_wgrad_reduce)(const float* __restrict__ part, float* __restrict__ grad_w, size_t total,
+                                                                        int splits DD_CONV_SCALE_PARAM) {
+  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= total) return;
+  float s = part[i];
+  for (int k = 1; k < splits; ++k) s += part[(size_t)k * total + i];
+  grad_w[i] = DD_CONV_UNSCALED(s);
+}
+
+#undef DD_CONV_KERNEL
+#undef DD_CONV_SCALE_PARAM
+#undef DD_CONV_GY
+#undef DD_CONV_UNSCALED

@@ -19,7 +19,7 @@ from torch import nn
 from . import modules as _modules
 from .batchnorm import convert_hip_batchnorm, resolve_bn_backend
 from .codec import convert_hip_codec, resolve_codec_backend
-from .conv import convert_hip_conv, resolve_conv_backend
+from .conv import convert_hip_conv, resolve_conv_backend, resolve_conv_grad_autoscale
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
 from .necks import HAHIHeteroNeck
 from .scheduler import DDIMScheduler
@@ -52,7 +52,7 @@ class DDIMDepthEstimate_Res(nn.Module):
 
     def __init__(self, in_channels=(64, 128, 256, 512), up_scale_factor=1, inference_steps=20, num_train_timesteps=1000,
                  return_indices=None, depth_transform_cfg=None, depth_feature_dim=16, detach_fp=False, loss_cfgs=(),
-                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, codec_backend=None, **kwargs):
+                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, codec_backend=None, conv_grad_autoscale=None, **kwargs):
         """Beyond the reference's keywords (src/model/diffusion_dcbase_model.py:77-91):
         profile            the two shipped configurations of a head (PROFILES below; None = $DDEPTH_PROFILE, else "reference"):
                              "reference" [default]  what the reference does, bit for bit where that is defined: fp32 arithmetic (the reference runs
@@ -86,6 +86,10 @@ class DDIMDepthEstimate_Res(nn.Module):
                            dd_convx_*): every FPN and neck convolution of every registered head is converted, the MPViT widths (216 / 288)
                            and Swin-L's 2048 -> 1536 ``trans_fusion.2`` included.  A site the block-64 contract takes runs the same kernels
                            and gives the same bits as with "hip" / "hip+neck"; on a Res head "hip+all" builds what "hip" builds.
+        conv_grad_autoscale  False [default] or True (None = $DDEPTH_CONV_GRAD_AUTOSCALE, "1" is on): the convolutions `conv_backend` converts
+                           rescale the incoming gradient by a power of two in their "f16" / "f16x3" backward (conv.py's docstring;
+                           include/ddepth_conv_scaled.h).  Switch it on for f16 / f16x3 training with conv_backend="hip*": a training step's
+                           gradients (about 3e-7) otherwise sit in f16's subnormals.  "bf16" does not need it and is not changed by it.
         codec_backend      "torch" [default] or "hip" (None = $DDEPTH_CODEC_BACKEND, else "torch"): with "hip" the four convolutions of
                            ``depth_transform`` become codec.HipCodecConv2d / codec.HipCodecConvTranspose2d holding the same tensors and the
                            decoder's nn.Sigmoid a codec.HipCodecTail, so their .train() forward and backward run in csrc/dd_codec.hip in
@@ -161,11 +165,13 @@ class DDIMDepthEstimate_Res(nn.Module):
                     setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
         self.conv_backend = resolve_conv_backend(conv_backend)
         channels = "any" if self.conv_backend == "hip+all" else "block64"
+        self.conv_grad_autoscale = resolve_conv_grad_autoscale(conv_grad_autoscale)
+        autoscale = (True,) if self.conv_grad_autoscale else ()      # (off: the calls there always were)
         if self.conv_backend in ("hip", "hip+neck", "hip+all"):
             # (convup_fp never runs; it is converted too, for uniformity)
             for name in ("conv_lateral", "conv_up", "convup_fp"):
                 if hasattr(self, name):
-                    setattr(self, name, convert_hip_conv(getattr(self, name), precision, False, channels))
+                    setattr(self, name, convert_hip_conv(getattr(self, name), precision, False, channels, *autoscale))
         self.codec_backend = resolve_codec_backend(codec_backend)
         if self.codec_backend == "hip":
             convert_hip_codec(self.depth_transform)
@@ -173,7 +179,7 @@ class DDIMDepthEstimate_Res(nn.Module):
             # the neck's 1x1 (lateral_convs, conv_proj, trans_proj) and 3x3 (conv_fusion, trans_fusion) convolutions; with "hip+neck", what the
             # block-64 contract does not take -- Swin-L's trans_fusion.2 with 2048 input channels, most MPViT widths -- stays nn.Conv2d; with
             # "hip+all" all twelve are converted
-            self.hahineck = convert_hip_conv(self.hahineck, precision, True, channels)
+            self.hahineck = convert_hip_conv(self.hahineck, precision, True, channels, *autoscale)
 
     @staticmethod
     def _on_hip(tensors) -> bool:

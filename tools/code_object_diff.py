@@ -2,6 +2,7 @@
 """Is the gfx950 device code of two builds the same?  For a refactor that must not change a kernel.
 
     python tools/code_object_diff.py OLD_BUILD_DIR NEW_BUILD_DIR        # two diffusiondepth_amd/_build directories (object files of build.py)
+    python tools/code_object_diff.py --allow-added OLD_BUILD_DIR NEW_BUILD_DIR      # for a change that may ADD kernels but not touch one
 
 Per translation unit: pulls the gfx950 code object out of each object file (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler
 --unbundle) and compares
@@ -10,7 +11,8 @@ Per translation unit: pulls the gfx950 code object out of each object file (llvm
   * the set of symbols (name, type, size; without that __hip_cuid_ name);
   * for every function its instruction stream (llvm-objdump -d without addresses and encodings), whatever the order the functions were emitted in;
   * for every kernel its amdhsa.kernels metadata entry (registers, LDS, scratch, arguments; llvm-readelf --notes).
-Exit status 0 when symbols, instruction streams and metadata agree for every unit.
+Exit status 0 when symbols, instruction streams and metadata agree for every unit.  With --allow-added a unit also passes when everything the
+OLD build holds is in the NEW one unchanged (symbol, instruction stream, metadata) and the new one only has more; the added kernels are counted.
 """
 from __future__ import annotations
 
@@ -65,7 +67,9 @@ def kernel_metadata(co):
 
 
 def main():
-    old, new = sys.argv[1], sys.argv[2]
+    argv = [a for a in sys.argv[1:] if a != "--allow-added"]
+    allow_added = len(argv) != len(sys.argv) - 1
+    old, new = argv[0], argv[1]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for o in sorted(f for f in os.listdir(old) if f.endswith(".o")):
@@ -78,6 +82,12 @@ def main():
             nf = sum(1 for k in set(fa) | set(fb) if fa.get(k) != fb.get(k))
             nk = sum(1 for k in set(ka) | set(kb) if ka.get(k) != kb.get(k))
             same = sa == sb and nf == 0 and nk == 0
+            # everything of the old build unchanged, the new one only has more
+            kept = all(sb.get(k) == v for k, v in sa.items()) and all(fb.get(k) == v for k, v in fa.items()) and all(kb.get(k) == v for k, v in ka.items())
+            if allow_added and kept and not same:
+                print("%-14s symbols %d / %d  functions %d / %d  kernels %d / %d: every symbol, instruction stream and metadata entry of the old build unchanged, "
+                      "%d kernels added  -> OLD DEVICE CODE IDENTICAL, KERNELS ADDED" % (o[:-2], len(sa), len(sb), len(fa), len(fb), len(ka), len(kb), len(set(kb) - set(ka))))
+                continue
             bad += not same
             print("%-14s sha256 %s / %s  symbols %d / %d %s  functions %d, differing %d  kernels %d, metadata differing %d  emission order %s  -> %s" % (
                 o[:-2], sha[0], sha[1], len(sa), len(sb), "same" if sa == sb else "DIFFER", len(fa), nf, len(ka), nk,

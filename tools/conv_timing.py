@@ -9,12 +9,18 @@
 
     python tools/conv_timing.py [--out profiles/conv_timing.json] [--windows 7] [--heads res,swin] [--sites lateral0,up1]
     python tools/conv_timing.py --channels any --heads mpvit      # the MPViT-small laterals through the extended channel range (dd_convx_*)
+    python tools/conv_timing.py --grad-autoscale                  # instead: each site's f16 / f16x3 backward with and without the rescale of grad_y
 
 Method: every variant of a site is warmed up; a timed window is CALLS forward + backward passes (input and weight gradient) between two device
 events; inside one repeat the variants are timed one after another (so drift hits all alike), and the median over the repeats is reported with
 min and max.  The three library calls of (c) are also timed one by one (a call = its pack or reduce launch plus the MFMA kernel) and set against
 both roofs: the bf16 MFMA peak from 2 * taps * Cin * Cout * B * H * W flops (taps = 9, or 4 for the transpose convolution), and the HBM peak from
 the bytes the algorithm needs (each tensor of the call once, fp32).  A measurement path that finds no GPU fails.
+
+--grad-autoscale (include/ddepth_conv_scaled.h; ``time_grad_autoscale`` below, shared with tools/neck_conv_timing.py) times, per site and for "f16"
+and "f16x3", in the same windows: the two gradient calls as they are; ``conv.grad_scale`` plus the two scaled calls (what ``grad_autoscale=True``
+runs); the amax pass alone; and each GEMM call against its scaled twin with a precomputed scale.  The comparison is the site's own unscaled
+backward from the same run; a twin is named slower only where its median exceeds the unscaled call's by more than the larger min-max spread.
 
 The whole training step is a command set, not part of this tool (bench.py decides how a step is measured):
     python bench.py --mode train-dp --variant res --batch 4              (also --variant swin)
@@ -74,9 +80,90 @@ def spread(v):
     return {"median_ms": statistics.median(v), "min_ms": min(v), "max_ms": max(v)}
 
 
+AUTOSCALE_PRECISIONS = ("f16", "f16x3")
+
+
+def time_grad_autoscale(op, xd, wd, gy, calls, windows, extra=()):
+    """{precision: {variant: spread, ...}} for one site: the backward (data + weight gradient) without and with the power-of-two rescale of
+    grad_y, the amax pass (conv.grad_scale) alone, and each GEMM call beside its scaled twin (scale computed beforehand)."""
+    out = {}
+    for prec in AUTOSCALE_PRECISIONS:
+        pid = CV.precision_id(prec)
+        s0 = CV.grad_scale(gy, pid)
+
+        def both(scale=None):
+            kw = {} if scale is None else {"scale": scale}
+            CV.conv_backward_data(op, gy, wd, xd.shape, pid, *extra, **kw)
+            CV.conv_backward_weight(op, xd, gy, wd.shape, pid, *extra, **kw)
+
+        fns = {"backward_unscaled": both, "backward_scaled": lambda: both(CV.grad_scale(gy, pid)), "grad_scale": lambda: CV.grad_scale(gy, pid),
+               "data_unscaled": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid, *extra),
+               "data_scaled": lambda: CV.conv_backward_data(op, gy, wd, xd.shape, pid, *extra, scale=s0),
+               "weight_unscaled": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid, *extra),
+               "weight_scaled": lambda: CV.conv_backward_weight(op, xd, gy, wd.shape, pid, *extra, scale=s0)}
+        for fn in fns.values():
+            for _ in range(2):
+                fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in fns}
+        for _ in range(windows):
+            for k, fn in fns.items():
+                times[k].append(window(fn, calls))
+        row = {k: spread(v) for k, v in times.items()}
+        width = lambda a, b: max(row[a]["max_ms"] - row[a]["min_ms"], row[b]["max_ms"] - row[b]["min_ms"])
+        row["grad_y_bytes"] = 4 * gy.numel()
+        row["grad_scale_hbm_share"] = row["grad_y_bytes"] / (row["grad_scale"]["median_ms"] * 1e-3) / HBM_PEAK
+        row["backward_extra_ms"] = row["backward_scaled"]["median_ms"] - row["backward_unscaled"]["median_ms"]
+        for g in ("data", "weight"):      # the scaled GEMM itself against its twin, beyond the run's own spread
+            row[g + "_twin_slower_beyond_spread"] = bool(row[g + "_scaled"]["median_ms"] > row[g + "_unscaled"]["median_ms"] + width(g + "_scaled", g + "_unscaled"))
+        out[prec] = row
+    return out
+
+
+def print_grad_autoscale(label, shape, res):
+    for prec, r in res.items():
+        print(f"{label:18s} {str(shape):28s} {prec:5s} backward ms  unscaled {r['backward_unscaled']['median_ms']:.3f}  scaled {r['backward_scaled']['median_ms']:.3f}"
+              f"  (amax pass {r['grad_scale']['median_ms']:.3f} = {100 * r['grad_scale_hbm_share']:.1f} % HBM)   data {r['data_unscaled']['median_ms']:.3f} -> "
+              f"{r['data_scaled']['median_ms']:.3f}   weight {r['weight_unscaled']['median_ms']:.3f} -> {r['weight_scaled']['median_ms']:.3f}"
+              + ("   TWIN SLOWER: " + ", ".join(g for g in ("data", "weight") if r[g + "_twin_slower_beyond_spread"])
+                 if r["data_twin_slower_beyond_spread"] or r["weight_twin_slower_beyond_spread"] else ""), flush=True)
+
+
+def main_grad_autoscale(args, extra):
+    want = set(filter(None, args.sites.split(",")))
+    rows = []
+    for head in filter(None, args.heads.split(",")):
+        for name, op, cin, cout, h, w in sites(head):
+            if want and name not in want:
+                continue
+            if not CV.supported(op, cin, cout, "f16", args.channels):
+                sys.exit(f"conv_timing: {name} {cin} -> {cout} is not supported with --channels {args.channels}")
+            s = 1 if op == CV.OP_CONV3X3 else 2
+            taps = 9 if op == CV.OP_CONV3X3 else 4
+            xd = torch.randn(B, cin, h, w, device="cuda")
+            wd = torch.randn((cout, cin, 3, 3) if op == CV.OP_CONV3X3 else (cin, cout, 2, 2), device="cuda") * 0.05
+            gy = torch.randn(B, cout, s * h, s * w, device="cuda") * 2.0 ** -20      # (a training step's magnitude: unscaled, the f16 operands of grad_y are subnormals)
+            calls = max(2, min(20, int(4e11 // (2.0 * taps * cin * cout * B * h * w))))
+            res = time_grad_autoscale(op, xd, wd, gy, calls, args.windows, extra)
+            print_grad_autoscale(f"{head} {name}", (B, cin, cout, h, w), res)
+            rows.append({"head": head, "site": name, "op": "conv3x3" if op == CV.OP_CONV3X3 else "deconv2x2", "shape": [B, cin, cout, h, w],
+                         "calls_per_window": calls, "windows": args.windows, "grad_autoscale": res})
+            del xd, wd, gy
+            torch.cuda.empty_cache()
+    result = {"tool": "conv_timing --grad-autoscale", "device": torch.cuda.get_device_name(0), "hbm_peak_bytes_per_s": HBM_PEAK, "channels": args.channels,
+              "sites": rows}
+    line = json.dumps(result)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out")
+    ap.add_argument("--grad-autoscale", action="store_true", help="time each site's f16 / f16x3 backward with and without the rescale of grad_y instead")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--heads", default="res,swin")
     ap.add_argument("--sites", default="")
@@ -88,6 +175,8 @@ def main():
     if args.windows < 5:
         sys.exit("conv_timing: at least five windows")
     torch.cuda.set_device(0)
+    if args.grad_autoscale:
+        return main_grad_autoscale(args, extra)
     want = set(filter(None, args.sites.split(",")))
     rows = []
     for head in filter(None, args.heads.split(",")):

@@ -15,6 +15,8 @@ convert_hip_conv(neck, "bf16", pointwise=True).
     python tools/neck_conv_timing.py --channels any      # the extended channel range (dd_convx_*): Swin-L trans_fusion.2 (2048 -> 1536) and the twelve
                                                          # neck sites of MPViT-small (128 / 216 / 288 / 288), plus the block-64 Swin-L sites again through
                                                          # channels="any" (same kernels: they should agree with the default run within its spread)
+    python tools/neck_conv_timing.py --grad-autoscale    # instead: each site's f16 / f16x3 backward with and without the rescale of grad_y
+                                                         # (include/ddepth_conv_scaled.h; the protocol of tools/conv_timing.py --grad-autoscale)
 
 Method: every variant of a site is warmed up; a timed window is CALLS forward + backward passes (input and weight gradient) between two device
 events; inside one repeat the variants are timed one after another (so drift hits all alike), and the median over the repeats is reported with
@@ -199,9 +201,41 @@ def time_neck(windows):
     return row
 
 
+def main_grad_autoscale(args):
+    from conv_timing import print_grad_autoscale, time_grad_autoscale      # (tools/ is this script's directory)
+    extra = (args.channels,) if args.channels != "block64" else ()
+    want = set(filter(None, args.sites.split(",")))
+    rows = []
+    for name, k, cin, cout, h, w in (sites_any() if args.channels == "any" else sites()):
+        if want and name not in want:
+            continue
+        op = CV.OP_CONV3X3 if k == 3 else CV.OP_CONV1X1
+        if not CV.supported(op, cin, cout, "f16", args.channels):
+            sys.exit(f"neck_conv_timing: {name} {cin} -> {cout} is not supported with --channels {args.channels}")
+        xd = torch.randn(B, cin, h, w, device="cuda")
+        wd = torch.randn(cout, cin, k, k, device="cuda") * 0.05
+        gy = torch.randn(B, cout, h, w, device="cuda") * 2.0 ** -20      # (a training step's magnitude: unscaled, the f16 operands of grad_y are subnormals)
+        calls = max(2, min(20, int(4e11 // (2.0 * k * k * cin * cout * B * h * w))))
+        res = time_grad_autoscale(op, xd, wd, gy, calls, args.windows, extra)
+        print_grad_autoscale(name, (B, cin, cout, h, w), res)
+        rows.append({"site": name, "op": "conv3x3" if k == 3 else "conv1x1", "shape": [B, cin, cout, h, w], "calls_per_window": calls,
+                     "windows": args.windows, "grad_autoscale": res})
+        del xd, wd, gy
+        torch.cuda.empty_cache()
+    result = {"tool": "neck_conv_timing --grad-autoscale", "channels": args.channels, "device": torch.cuda.get_device_name(0),
+              "hbm_peak_bytes_per_s": HBM_PEAK, "sites": rows}
+    line = json.dumps(result)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--out")
+    ap.add_argument("--grad-autoscale", action="store_true", help="time each site's f16 / f16x3 backward with and without the rescale of grad_y instead")
     ap.add_argument("--windows", type=int, default=7)
     ap.add_argument("--sites", default="")
     ap.add_argument("--no-neck", action="store_true")
@@ -212,6 +246,8 @@ def main():
     if args.windows < 5:
         sys.exit("neck_conv_timing: at least five windows")
     torch.cuda.set_device(0)
+    if args.grad_autoscale:
+        return main_grad_autoscale(args)
     want = set(filter(None, args.sites.split(",")))
     rows = []
     for site in (sites_any() if args.channels == "any" else sites()):
