@@ -25,6 +25,13 @@ multiplies ``grad_y`` by a power of two taken from its largest finite magnitude 
 (include/ddepth_conv_scaled.h): nothing else changes, and "bf16" is left as it is.  Off by default -- today's calls and today's bits:
 
     convert_hip_conv(head.conv_lateral, "f16x3", grad_autoscale=True)      # or: conv_grad_autoscale=True / DDEPTH_CONV_GRAD_AUTOSCALE=1
+
+The backbone (opt-in, ``strided``).  model.ResNetForMMBEV opens every stage with two 3x3 stride-2 pad-1 convolutions, ``conv1`` and the biased
+``downsample``, the first of them on the three RGB planes.  ``HipConv2d`` marked ``strided = True`` runs them through include/ddepth_conv_strided.h
+(dd_conv3x3s2_*: bias in the epilogue, its gradient from the weight gradient's call, Cin 3 or a multiple of 8); the converter marks a module only
+when asked to, and the default replaces exactly what it always replaced:
+
+    convert_hip_conv(backbone, "bf16", channels="any", strided=True)       # or: args.backbone_backend="hip" / DDEPTH_BACKBONE_BACKEND=hip
 """
 from __future__ import annotations
 
@@ -48,6 +55,10 @@ ABI_SYMBOLS = ["dd_conv_last_error", "dd_conv_supported", "dd_conv_workspace_byt
 # every symbol include/ddepth_conv_scaled.h declares (tests/test_conv_scaled_cpu.py); bound on first use, so ABI_SYMBOLS and _lib() stay what they were
 ABI_SYMBOLS_SCALED = ["dd_conv_grad_scale", "dd_convx_backward_data_scaled", "dd_convx_backward_weight_scaled"]
 
+# every symbol include/ddepth_conv_strided.h declares (tests/test_conv_strided_cpu.py): the 3x3 stride-2 operator; bound on first use as well
+ABI_SYMBOLS_STRIDED = ["dd_conv3x3s2_supported", "dd_conv3x3s2_workspace_bytes", "dd_conv3x3s2_forward", "dd_conv3x3s2_backward_data",
+                       "dd_conv3x3s2_backward_weight"]
+
 OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
 _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
@@ -63,6 +74,7 @@ _ENTRY_SCALED = (None, "dd_convx_backward_data_scaled", "dd_convx_backward_weigh
 
 _bound = None
 _bound_scaled = None
+_bound_strided = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
 
@@ -100,6 +112,21 @@ def _lib_scaled():
             f.restype, f.argtypes = c_int, [c_int] + [c_vp] * 5 + [c_int] * 6 + [c_vp]
         _bound_scaled = lib
     return _bound_scaled
+
+
+def _lib_strided():
+    global _bound_strided
+    if _bound_strided is None:
+        lib = _lib()
+        c_int, c_vp = ctypes.c_int, ctypes.c_void_p
+        lib.dd_conv3x3s2_supported.restype, lib.dd_conv3x3s2_supported.argtypes = c_int, [c_int] * 3
+        lib.dd_conv3x3s2_workspace_bytes.restype = c_int
+        lib.dd_conv3x3s2_workspace_bytes.argtypes = [c_int] * 6 + [ctypes.POINTER(ctypes.c_int64)]
+        lib.dd_conv3x3s2_forward.restype, lib.dd_conv3x3s2_forward.argtypes = c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp]
+        lib.dd_conv3x3s2_backward_data.restype, lib.dd_conv3x3s2_backward_data.argtypes = c_int, [c_vp] * 5 + [c_int] * 6 + [c_vp]
+        lib.dd_conv3x3s2_backward_weight.restype, lib.dd_conv3x3s2_backward_weight.argtypes = c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp]
+        _bound_strided = lib
+    return _bound_strided
 
 
 def _ck(rc, what):
@@ -303,6 +330,129 @@ class ConvTranspose2x2Function(Function):
         return _backward(ctx, grad_y)
 
 
+# ---- 3x3 stride 2 pad 1, with or without a bias (include/ddepth_conv_strided.h): the opening convolutions of a ResNet stage ------------------------
+def supported_s2(cin: int, cout: int, precision, channels="any") -> bool:
+    """dd_conv3x3s2_supported (Cout a multiple of 8 in 8..2048, Cin 3 or such a multiple); ``channels="block64"`` narrows it to the block-64
+    shapes.  No device needed, no side effects."""
+    p = precision_id(precision)
+    if p is None or not bool(_lib_strided().dd_conv3x3s2_supported(int(cin), int(cout), p)):
+        return False
+    return _any(channels) or all(c % 64 == 0 and 64 <= c <= 1536 for c in (int(cin), int(cout)))
+
+
+def strided_out(n: int) -> int:
+    """Output rows (columns) of k3 s2 p1 on n input rows (columns)."""
+    return (int(n) - 1) // 2 + 1
+
+
+def _s2_geometry(x: torch.Tensor, w: torch.Tensor):
+    if x.dim() != 4 or w.dim() != 4:
+        raise ValueError(f"expected 4D input and weight (got {x.dim()}D, {w.dim()}D)")
+    B, cin, H, W = (int(s) for s in x.shape)
+    if int(w.shape[1]) != cin or tuple(w.shape[2:]) != (3, 3):
+        raise ValueError(f"weight {tuple(w.shape)} does not fit input {tuple(x.shape)}")
+    return B, cin, int(w.shape[0]), H, W
+
+
+def _s2_workspace(t, dims, prec):
+    need = ctypes.c_int64(0)
+    _ck(_lib_strided().dd_conv3x3s2_workspace_bytes(*dims, prec, ctypes.byref(need)), "dd_conv3x3s2_workspace_bytes")
+    key = (t.device.index if t.device.index is not None else torch.cuda.current_device(), int(need.value))
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = torch.empty(int(need.value), dtype=torch.uint8, device=t.device)
+        _workspaces[key] = ws
+    return ws
+
+
+def _check_vector(t, name, n, like):
+    if t is not None:
+        _check_native(t, name)
+        if t.dim() != 1 or t.numel() != n or t.device != like.device:
+            raise ValueError(f"{name} must have {n} elements on {like.device} (got {tuple(t.shape)} on {t.device})")
+
+
+def conv_s2_forward(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], prec: int) -> torch.Tensor:
+    """F.conv2d(x, w, bias, 2, 1) through dd_conv3x3s2_forward; ``bias`` may be None."""
+    _check_native(x, "x")
+    _check_native(w, "weight")
+    dims = _s2_geometry(x, w)
+    B, _, cout, H, W = dims
+    _check_vector(bias, "bias", cout, x)
+    y = torch.empty((B, cout, strided_out(H), strided_out(W)), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = _s2_workspace(x, dims, int(prec))
+        _ck(_lib_strided().dd_conv3x3s2_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
+                                                ws.data_ptr(), *dims, int(prec), _stream(x)), "dd_conv3x3s2_forward")
+    return y
+
+
+def conv_s2_backward_data(grad_y: torch.Tensor, w: torch.Tensor, x_shape, prec: int, *, scale=None) -> torch.Tensor:
+    """The data gradient; ``scale``: a ``grad_scale`` tensor or None, as in ``conv_backward_data``."""
+    _check_native(grad_y, "grad_y")
+    _check_native(w, "weight")
+    _check_scale(scale, grad_y)
+    grad_x = torch.empty(tuple(x_shape), dtype=torch.float32, device=grad_y.device)
+    dims = _s2_geometry(grad_x, w)
+    if tuple(grad_y.shape) != (dims[0], dims[2], strided_out(dims[3]), strided_out(dims[4])):
+        raise ValueError(f"grad_y {tuple(grad_y.shape)} does not fit input {tuple(x_shape)} and weight {tuple(w.shape)}")
+    with torch.cuda.device(grad_y.device):
+        ws = _s2_workspace(grad_y, dims, int(prec))
+        _ck(_lib_strided().dd_conv3x3s2_backward_data(grad_y.data_ptr(), w.data_ptr(), grad_x.data_ptr(), ws.data_ptr(),
+                                                      scale.data_ptr() if scale is not None else None, *dims, int(prec), _stream(grad_y)),
+            "dd_conv3x3s2_backward_data")
+    return grad_x
+
+
+def conv_s2_backward_weight(x: torch.Tensor, grad_y: torch.Tensor, w_shape, prec: int, *, with_bias: bool = False, scale=None):
+    """(grad_w, grad_bias) from ONE call; grad_bias is None unless ``with_bias``."""
+    _check_native(x, "x")
+    _check_native(grad_y, "grad_y")
+    _check_scale(scale, grad_y)
+    grad_w = torch.empty(tuple(w_shape), dtype=torch.float32, device=x.device)
+    dims = _s2_geometry(x, grad_w)
+    if tuple(grad_y.shape) != (dims[0], dims[2], strided_out(dims[3]), strided_out(dims[4])):
+        raise ValueError(f"grad_y {tuple(grad_y.shape)} does not fit input {tuple(x.shape)} and weight {tuple(w_shape)}")
+    grad_b = torch.empty(dims[2], dtype=torch.float32, device=x.device) if with_bias else None
+    with torch.cuda.device(x.device):
+        ws = _s2_workspace(x, dims, int(prec))
+        _ck(_lib_strided().dd_conv3x3s2_backward_weight(x.data_ptr(), grad_y.data_ptr(), grad_w.data_ptr(),
+                                                        grad_b.data_ptr() if grad_b is not None else None, ws.data_ptr(),
+                                                        scale.data_ptr() if scale is not None else None, *dims, int(prec), _stream(x)),
+            "dd_conv3x3s2_backward_weight")
+    return grad_w, grad_b
+
+
+class Conv3x3S2Function(Function):
+    """(x, weight, bias or None, dd_precision[, grad_autoscale]) -> F.conv2d(x, weight, bias, 2, 1) over the three dd_conv3x3s2_* calls.  Kept for
+    the backward: x and weight only.  A gradient ``ctx.needs_input_grad`` does not ask for is not computed (the RGB image needs no data
+    gradient); the bias gradient comes from the same call as the weight gradient.  Nothing synchronises the host."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, prec, grad_autoscale=False):
+        ctx.save_for_backward(x, weight)
+        ctx.prec = int(prec)
+        ctx.grad_autoscale = bool(grad_autoscale)
+        return conv_s2_forward(x, weight.detach(), bias.detach() if bias is not None else None, int(prec))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, weight = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_x or need_w or need_b):
+            return None, None, None, None, None
+        gy = grad_y.detach()
+        if gy.dtype != torch.float32 or not gy.is_contiguous():
+            gy = gy.float().contiguous()
+        scaled = {"scale": grad_scale(gy, ctx.prec)} if ctx.grad_autoscale else {}      # once per backward
+        gx = conv_s2_backward_data(gy, weight.detach(), x.shape, ctx.prec, **scaled) if need_x else None
+        gw = gb = None
+        if need_w or need_b:      # (one call serves both; a frozen weight with a live bias still runs it)
+            gw, gb = conv_s2_backward_weight(x, gy, weight.shape, ctx.prec, with_bias=need_b, **scaled)
+        return gx, gw if need_w else None, gb, None, None
+
+
 def _tensors_native(x: torch.Tensor, w: torch.Tensor) -> bool:
     return bool(x.is_cuda and w.is_cuda and x.dim() == 4 and x.dtype == torch.float32 and w.dtype == torch.float32 and x.is_contiguous()
                 and w.is_contiguous() and x.numel() > 0)
@@ -320,6 +470,13 @@ def _plain(m) -> bool:
 def _is_conv3x3(m) -> bool:
     return (isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and _plain(m) and _pair(m.kernel_size) == (3, 3)
             and _pair(m.stride) == (1, 1) and m.padding != "same" and _pair(m.padding) == (1, 1))
+
+
+def _is_conv3x3s2(m) -> bool:
+    """3x3, stride 2, pad 1, dilation 1, groups 1, zero padding; a bias is allowed."""
+    return (isinstance(m, nn.Conv2d) and not isinstance(m, nn.ConvTranspose2d) and m.groups == 1 and _pair(m.dilation) == (1, 1)
+            and getattr(m, "padding_mode", "zeros") == "zeros" and _pair(m.kernel_size) == (3, 3) and _pair(m.stride) == (2, 2)
+            and m.padding != "same" and _pair(m.padding) == (1, 1))
 
 
 def _is_conv1x1(m) -> bool:
@@ -353,13 +510,24 @@ class HipConv2d(nn.Conv2d):
 
     channels = "block64"      # the channel contract (CHANNELS); a class attribute, so modules made before it existed behave as they did
     grad_autoscale = False    # rescale grad_y by a power of two in the "f16" / "f16x3" backward (module docstring); likewise a class attribute
+    strided = False           # True: a 3x3 stride-2 pad-1 geometry, with or without a bias, runs dd_conv3x3s2_* (convert_hip_conv(..., strided=True))
 
     def __init__(self, in_channels, out_channels, kernel_size=3, stride=1, padding=1, bias=False, precision="fp32", **kwargs):
         super().__init__(in_channels, out_channels, kernel_size, stride, padding, bias=bias, **kwargs)
         self.precision = precision
 
     def extra_repr(self):
-        return super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels) + _autoscale_repr(self.grad_autoscale)
+        return (super().extra_repr() + f", precision={self.precision}" + _channels_repr(self.channels) + _autoscale_repr(self.grad_autoscale)
+                + (", strided=True" if self.strided else ""))
+
+    def _native_s2(self, x) -> bool:
+        """Whether this call runs the stride-2 operator of the library."""
+        if not (self.strided and _is_conv3x3s2(self) and _tensors_native(x, self.weight) and x.shape[1] == self.in_channels):
+            return False
+        b = self.bias
+        if b is not None and not (b.is_cuda and b.dtype == torch.float32 and b.is_contiguous()):
+            return False
+        return supported_s2(self.in_channels, self.out_channels, self.precision, self.channels)
 
     def _native(self, x) -> Optional[int]:
         """The dd_conv_op this call runs in the library, or None for the torch forward."""
@@ -370,6 +538,8 @@ class HipConv2d(nn.Conv2d):
         return op
 
     def forward(self, x):
+        if self.strided and self._native_s2(x):
+            return Conv3x3S2Function.apply(x, self.weight, self.bias, precision_id(self.precision), self.grad_autoscale)
         op = self._native(x)
         if op is None:
             return super().forward(x)
@@ -400,11 +570,14 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
         return _apply(ConvTranspose2x2Function, x, self.weight, precision_id(self.precision), self.channels, self.grad_autoscale)
 
 
-def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64") -> bool:
+def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64", strided: bool = False) -> bool:
     """3x3 s1 p1 or transpose k2 s2 (with ``pointwise``: or 1x1 s1 p0), no bias, groups 1, dilation 1, and channel counts and a precision
-    dd_conv_supported (``channels="any"``: dd_convx_supported) accepts."""
+    dd_conv_supported (``channels="any"``: dd_convx_supported) accepts.  With ``strided``: also 3x3 s2 p1, with or without a bias, that
+    dd_conv3x3s2_supported accepts (``channels="block64"``: its block-64 shapes only)."""
     if isinstance(m, (HipConv2d, HipConvTranspose2d)):
         return False
+    if strided and _is_conv3x3s2(m):
+        return supported_s2(m.in_channels, m.out_channels, precision, channels)
     if pointwise and _is_conv1x1(m):
         return supported(OP_CONV1X1, m.in_channels, m.out_channels, precision, channels)
     if _is_conv3x3(m):
@@ -426,20 +599,25 @@ def _from_conv(m, precision, channels="block64", grad_autoscale=False):
         out.channels = channels
     if grad_autoscale:
         out.grad_autoscale = True
+    if cls is HipConv2d and _is_conv3x3s2(m):      # (only convert_hip_conv(..., strided=True) finds such a module eligible)
+        out.strided = True
     return out
 
 
-def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False, channels="block64", grad_autoscale: bool = False) -> nn.Module:
+def convert_hip_conv(module: nn.Module, precision, pointwise: bool = False, channels="block64", grad_autoscale: bool = False,
+                     strided: bool = False) -> nn.Module:
     """Every eligible convolution of ``module`` (see ``eligible``) becomes a ``HipConv2d`` / ``HipConvTranspose2d`` holding the SAME parameter
     tensor under the same name: state-dict keys and the indices inside an ``nn.Sequential`` do not change.  With a precision the library does
     not run ("fp32", "f16r", "naive_fp32") or channel counts it does not support nothing is eligible and nothing is replaced.  A 1x1
     convolution is replaced only with ``pointwise=True`` (the HAHI neck); the default leaves every 1x1 an ``nn.Conv2d``.  ``channels="any"``
     takes every multiple of 8 in 8..2048 (MPViT's 216 / 288, Swin-L's 2048 -> 1536) and marks the new modules with it; the default keeps
     the block-64 contract, multiples of 64 in 64..1536.  ``grad_autoscale=True`` marks the new modules so that their "f16" / "f16x3" backward
-    rescales the incoming gradient by a power of two (module docstring); the default leaves the backward as it is."""
-    out = _from_conv(module, precision, channels, grad_autoscale) if eligible(module, precision, pointwise, channels) else module
+    rescales the incoming gradient by a power of two (module docstring); the default leaves the backward as it is.  ``strided=True`` also takes
+    the 3x3 stride-2 pad-1 convolutions, biased ones included (the openings of a ResNet stage: ``conv1`` and ``downsample`` of
+    model.ResNetForMMBEV), and marks them ``strided``; the default leaves every one of them an ``nn.Conv2d``."""
+    out = _from_conv(module, precision, channels, grad_autoscale) if eligible(module, precision, pointwise, channels, strided) else module
     for name, child in list(module.named_children()):
-        new = convert_hip_conv(child, precision, pointwise, channels, grad_autoscale)
+        new = convert_hip_conv(child, precision, pointwise, channels, grad_autoscale, strided)
         if new is not child:
             setattr(out, name, new)
     return out

@@ -1,8 +1,9 @@
-// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h and include/ddepth_conv_scaled.h: argument checks and the launch sequence; the kernels
-// are in dd_conv.hip.
+// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h, include/ddepth_conv_scaled.h and include/ddepth_conv_strided.h: argument checks and the
+// launch sequence; the kernels are in dd_conv.hip.
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_conv.h"
 #include "../../include/ddepth_conv_scaled.h"
+#include "../../include/ddepth_conv_strided.h"
 #include "dd_conv.h"
 #include "dd_status.h"
 
@@ -75,6 +76,21 @@ int run_wgrad(ChannelContract contract, int op, const float* x, const float* gra
   if (int rc = ddstatus::check_ptrs(g_conv_err, x, grad_y, grad_w, ws)) return rc;
   if (scaled && !scale) return g_conv_err.fail(DD_ERR_INVALID_ARG, "scale is NULL");
   DD_STATUS_HIP(g_conv_err, ddconv::launch_wgrad(op, x, grad_y, grad_w, ws, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
+  return DD_OK;
+}
+
+// include/ddepth_conv_strided.h: everything but the pointers; leaves the kernels' mode in *prec
+int check_s2(int B, int Cin, int Cout, int H, int W, int precision, int* prec) {
+  *prec = kernel_prec(precision);
+  if (*prec < 0)
+    return g_conv_err.fail(DD_ERR_UNSUPPORTED, "precision %d is unsupported: this operator runs DD_PREC_BF16, DD_PREC_F16 and DD_PREC_F16X3", precision);
+  if (!ddconv::channels_s2_in(Cin) || !ddconv::channels_extended(Cout))
+    return g_conv_err.fail(DD_ERR_UNSUPPORTED, "Cin = %d, Cout = %d are unsupported: Cout a multiple of 8 in 8..2048, Cin 3 or a multiple of 8 in 8..2048",
+                           Cin, Cout);
+  if (B < 1 || H < 1 || W < 1) return g_conv_err.fail(DD_ERR_INVALID_ARG, "B, H, W must be positive (got %d, %d, %d)", B, H, W);
+  if (B > 65535) return g_conv_err.fail(DD_ERR_INVALID_ARG, "B = %d: at most 65535 per call", B);
+  if ((int64_t)H * (int64_t)W > (int64_t)INT_MAX / 4 || H > INT_MAX / 4 || W > INT_MAX / 4)
+    return g_conv_err.fail(DD_ERR_INVALID_ARG, "H = %d, W = %d: 4 * H * W must fit an int", H, W);
   return DD_OK;
 }
 
@@ -177,6 +193,50 @@ int dd_convx_backward_data_scaled(int op, const float* grad_y, const float* w, f
 int dd_convx_backward_weight_scaled(int op, const float* x, const float* grad_y, float* grad_w, void* workspace, const float* scale, int B, int Cin,
                                     int Cout, int H, int W, int precision, void* stream) {
   return run_wgrad(kChannelsExtended, op, x, grad_y, grad_w, workspace, B, Cin, Cout, H, W, precision, stream, true, scale);
+}
+
+// ---- include/ddepth_conv_strided.h: 3x3 stride 2 pad 1, optional bias ----------------------------------------------------------------------------------
+int dd_conv3x3s2_supported(int Cin, int Cout, int precision) {
+  return (kernel_prec(precision) >= 0 && ddconv::channels_s2_in(Cin) && ddconv::channels_extended(Cout)) ? 1 : 0;
+}
+
+int dd_conv3x3s2_workspace_bytes(int B, int Cin, int Cout, int H, int W, int precision, int64_t* bytes) {
+  if (!bytes) return g_conv_err.fail(DD_ERR_INVALID_ARG, "bytes is NULL");
+  int prec = 0;
+  if (int rc = check_s2(B, Cin, Cout, H, W, precision, &prec)) return rc;
+  *bytes = (int64_t)ddconv::workspace_bytes_s2(B, Cin, Cout, H, W, prec);
+  return DD_OK;
+}
+
+int dd_conv3x3s2_forward(const float* x, const float* w, const float* bias, float* y, void* workspace, int B, int Cin, int Cout, int H, int W,
+                         int precision, void* stream) {
+  int prec = 0;
+  if (int rc = check_s2(B, Cin, Cout, H, W, precision, &prec)) return rc;
+  if (int rc = ddstatus::check_ptrs(g_conv_err, x, w, y, workspace)) return rc;
+  if (bias && (const void*)bias == (const void*)y) return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv_s2_forward(x, w, bias, y, workspace, B, Cin, Cout, H, W, prec, (hipStream_t)stream));
+  return DD_OK;
+}
+
+int dd_conv3x3s2_backward_data(const float* grad_y, const float* w, float* grad_x, void* workspace, const float* scale, int B, int Cin, int Cout,
+                               int H, int W, int precision, void* stream) {
+  int prec = 0;
+  if (int rc = check_s2(B, Cin, Cout, H, W, precision, &prec)) return rc;
+  if (int rc = ddstatus::check_ptrs(g_conv_err, grad_y, w, grad_x, workspace)) return rc;
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv_s2_dgrad(grad_y, w, grad_x, workspace, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
+  return DD_OK;
+}
+
+int dd_conv3x3s2_backward_weight(const float* x, const float* grad_y, float* grad_w, float* grad_bias, void* workspace, const float* scale, int B,
+                                 int Cin, int Cout, int H, int W, int precision, void* stream) {
+  int prec = 0;
+  if (int rc = check_s2(B, Cin, Cout, H, W, precision, &prec)) return rc;
+  if (int rc = ddstatus::check_ptrs(g_conv_err, x, grad_y, grad_w, workspace)) return rc;
+  if (grad_bias && ((const void*)grad_bias == (const void*)x || (const void*)grad_bias == (const void*)grad_y || grad_bias == grad_w))
+    return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  DD_STATUS_HIP(g_conv_err,
+                ddconv::launch_conv_s2_wgrad(x, grad_y, grad_w, grad_bias, workspace, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
+  return DD_OK;
 }
 
 }  // extern "C"

@@ -59,4 +59,20 @@ hipError_t launch_wgrad(int op, const float* x, const float* grad_y, float* grad
 constexpr int kGradAmaxExp = 14;      // s * amax < 2^15 <= 65504, the largest f16: one GEMM accumulates in fp32, nothing behind it can overflow
 hipError_t launch_grad_scale(const float* grad_y, int64_t n, int prec, int amax_exp, float* scale, hipStream_t st);
 
+// ---- the 3x3 stride 2 pad 1 operator of include/ddepth_conv_strided.h ----------------------------------------------------------------------------------
+// Not a dd_conv_op: the ABI of ddepth_conv.h keeps its three.  Inside this unit it is a fourth row of the one GEMM table.
+enum { kOpConv3S2 = 3 };
+// its channel contract: Cout extended; Cin extended or 3 (the guarded kernels check every channel, the weight image is padded to the K step)
+constexpr bool channels_s2_in(int c) { return c == 3 || channels_extended(c); }
+constexpr int strided_out(int n) { return (n - 1) / 2 + 1; }      // Ho of H: k3 s2 p1
+
+// H, W = the INPUT size everywhere.  bias / grad_bias / scale may be NULL; scale as in launch_conv (the two gradients of the f16 modes).
+size_t workspace_bytes_s2(int B, int Cin, int Cout, int H, int W, int prec);
+hipError_t launch_conv_s2_forward(const float* x, const float* w, const float* bias, float* y, void* workspace, int B, int Cin, int Cout, int H, int W,
+                                  int prec, hipStream_t st);
+hipError_t launch_conv_s2_dgrad(const float* grad_y, const float* w, float* grad_x, void* workspace, int B, int Cin, int Cout, int H, int W, int prec,
+                                hipStream_t st, const float* scale);
+hipError_t launch_conv_s2_wgrad(const float* x, const float* grad_y, float* grad_w, float* grad_bias, void* workspace, int B, int Cin, int Cout, int H,
+                                int W, int prec, hipStream_t st, const float* scale);
+
 }  // namespace ddconv

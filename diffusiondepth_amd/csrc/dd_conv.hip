@@ -23,6 +23,10 @@
 //   the five kernels above  live in dd_conv_kernels.h, included twice: as they are, and as the twins *_scaled_kernel that multiply grad_y by the power of two
 //                           scale[0] before it is rounded and the result by scale[1] = 1 / scale[0] (include/ddepth_conv_scaled.h; f16 modes, the two
 //                           gradients).  dd_conv_grad_amax_kernel / dd_conv_grad_scale_pair_kernel make that pair on the device.
+//   3x3 stride 2 pad 1      include/ddepth_conv_strided.h (the openings of a ResNet stage, bias allowed, Cin = 3 allowed): the forward is dd_conv_igemm <3, 2, 1>
+//                           from a third inclusion of the header that adds the bias to the epilogue (dd_conv_igemm_bias_kernel), the weight gradient is
+//                           dd_conv_wgrad <3, 2, 1>; the data gradient is dd_conv_s2_dgrad_kernel, which sorts the nine taps by the parity of the input pixel
+//                           (1 + 2 + 2 + 4 tap GEMMs per 2 x 2 pixels); dd_conv_bias_grad_kernel / _reduce_kernel sum grad_y per channel in fp64 in a fixed order.
 //   host side               gemm_kind(op, dir) is the one table of <KS, S, PAD, KC, SCATTER> and pack mode, gemm_shape adds N and K; the pack launch,
 //                           the GEMM launch, packed_halfs and workspace_bytes read them, so the three that must agree on the padded weight image to
 //                           the byte cannot drift apart.  dispatch() turns the runtime operand mode and channel contract into template arguments.
@@ -83,7 +87,7 @@ __device__ __forceinline__ f32x16_t mma_pair(const uint4& ah, const uint4& al, c
 }
 
 // ---- weights -> wp[tap][n][k], 16 bits ----------------------------------------------------------------------------------------------------------
-enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3, kPackPwFwd = 4, kPackPwBwd = 5 };
+enum { kPackConvFwd = 0, kPackConvBwd = 1, kPackDeconvFwd = 2, kPackDeconvBwd = 3, kPackPwFwd = 4, kPackPwBwd = 5, kPackConvS2Bwd = 6 };
 
 // RAGGED: the image is wp[tap][Np][Kp] with Np = N rounded up to kTileN and Kp = K rounded up to the GEMM's K step `kstep`; every element of it is
 // written on every call, zero where n >= N or k >= K (the workspace arrives with arbitrary contents), so every 16-byte read of the GEMM kernels
@@ -115,8 +119,10 @@ __global__ __launch_bounds__(kThreads) void dd_conv_pack_kernel(const float* __r
     src = ((size_t)n * K + k) * 4 + t;
   } else if (mode == kPackPwFwd) {        // 1x1: w[co = n][ci = k]
     src = (size_t)n * K + k;
-  } else {                                // 1x1 data gradient: w'[ci = n][co = k] = w[co][ci]
+  } else if (mode == kPackPwBwd) {        // 1x1 data gradient: w'[ci = n][co = k] = w[co][ci]
     src = (size_t)k * N + n;
+  } else {                                // 3x3 stride 2 data gradient: w'[ci = n][co = k][ky][kx] = w[co][ci][ky][kx], the taps by parity class in the kernel
+    src = ((size_t)k * N + n) * 9 + t;
   }
   uint16_t hi, lo;
   to_operand<PREC>(w[src], hi, lo);
@@ -131,11 +137,18 @@ constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channe
 }
 
 #define DD_CONV_SCALED 0
+#define DD_CONV_BIAS 0
 #include "dd_conv_kernels.h"
 #undef DD_CONV_SCALED
 #define DD_CONV_SCALED 1
 #include "dd_conv_kernels.h"
 #undef DD_CONV_SCALED
+#undef DD_CONV_BIAS
+#define DD_CONV_SCALED 0
+#define DD_CONV_BIAS 1      // dd_conv_igemm_bias_kernel: the forward of include/ddepth_conv_strided.h
+#include "dd_conv_kernels.h"
+#undef DD_CONV_SCALED
+#undef DD_CONV_BIAS
 
 // ---- the scale of a gradient (include/ddepth_conv_scaled.h) -------------------------------------------------------------------------------------------
 // scale[2] = the bits of the largest FINITE |g[i]|, as an integer maximum of the bits of the non-negative floats (their order is that of the
@@ -191,6 +204,9 @@ struct GemmKind {
 constexpr GemmKind gemm_kind(int op, int dir) {
   if (op == kOpConv3) return {3, 1, 1, 32, dir == 0 ? kPackConvFwd : kPackConvBwd, false};
   if (op == kOpConv1) return {1, 1, 0, kPwKStep, dir == 0 ? kPackPwFwd : kPackPwBwd, false};
+  // 3x3 s2 p1.  Forward: the 9 x 65 pixel patch at KC = 16 is 28 KB of LDS (56 KB split-f16), so two workgroups still share a CU in the split mode;
+  // KC = 32 (46.8 / 93.6 KB) would leave one.  Data gradient: dd_conv_s2_dgrad_kernel, a 5 x 33 patch, KC = 32 (13.2 / 26.4 KB).
+  if (op == kOpConv3S2) return {3, 2, 1, dir == 0 ? 16 : 32, dir == 0 ? kPackConvFwd : kPackConvS2Bwd, false};
   if (dir == 0) return {1, 1, 0, 32, kPackDeconvFwd, true};      // N = 4 Cout: GEMM column (dy * 2 + dx) * Cout + co, scattered by the epilogue
   return {2, 2, 0, 16, kPackDeconvBwd, false};                   // ... and gathered again: four taps of stride 2
 }
@@ -211,7 +227,7 @@ size_t packed_halfs(const GemmShape& g) { return (size_t)g.taps * (size_t)padded
 // the weight gradient: taps of the filter itself (those of the data gradient's GEMM; the transpose forward folds its four into N), and the rows RH of
 // a pixel tile of its instantiation (LDS: 58.5 KB / 43.5 KB split-f16; the 1x1 has flat tiles)
 constexpr int taps_of(int op) { return gemm_kind(op, 1).ks * gemm_kind(op, 1).ks; }
-constexpr int wgrad_rows(int op) { return op == kOpConv3 ? 2 : 1; }
+constexpr int wgrad_rows(int op) { return op == kOpConv3 || op == kOpConv3S2 ? 2 : 1; }
 
 // the implicit GEMM of (OP, DIR), instantiated from its gemm_kind.  H, W = the tile grid (the forward's input size); the input is `stride` times that.
 // SCALED: the twin that rescales `in` (grad_y) by `scale`; data gradients only.
@@ -324,6 +340,84 @@ hipError_t dispatch(int prec, int Cin, int Cout, bool scaled, F f) {
   return by_scale(std::integral_constant<int, kPrecF16x3>{});
 }
 
+// ---- 3x3 stride 2 (include/ddepth_conv_strided.h) ----------------------------------------------------------------------------------------------------
+// dir 0: pack, then the implicit GEMM <3, 2, 1> with the bias in its epilogue; dir 1: pack by tap, then the parity-class kernel (SCALED: its twin)
+template <int PREC, bool RAGGED, bool SCALED>
+hipError_t launch_s2_prec(int dir, const float* in, const float* w, const float* bias, float* out, void* workspace, const float* scale, int B,
+                          int Cin, int Cout, int H, int W, hipStream_t st) {
+  const GemmShape g = gemm_shape(kOpConv3S2, dir, Cin, Cout);
+  const int Ho = strided_out(H), Wo = strided_out(W);      // also the half-resolution grid of the data gradient: ceil(H / 2) x ceil(W / 2)
+  uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
+  uint16_t* wl = wh + packed_halfs(g);
+  hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(packed_halfs(g))), dim3(kThreads), 0, st, w, wh, wl, g.pack_mode, g.N, g.K,
+                     g.taps, g.kstep);
+  const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
+  const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)((g.N + kTileN - 1) / kTileN), (unsigned)B);
+  if (dir == 0) {
+    constexpr GemmKind k = gemm_kind(kOpConv3S2, 0);
+    hipLaunchKernelGGL((dd_conv_igemm_bias_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>), grid, dim3(kThreads), 0, st, in,
+                       (const uint16_t*)wh, (const uint16_t*)wl, out, g.K, g.N, H, W, Ho, Wo, tiles_x, bias);
+  } else {
+    constexpr GemmKind k = gemm_kind(kOpConv3S2, 1);
+    if constexpr (SCALED) {
+      hipLaunchKernelGGL((dd_conv_s2_dgrad_scaled_kernel<PREC, k.kstep, RAGGED>), grid, dim3(kThreads), 0, st, in, (const uint16_t*)wh,
+                         (const uint16_t*)wl, out, g.K, g.N, H, W, Ho, Wo, tiles_x, scale);
+    } else {
+      hipLaunchKernelGGL((dd_conv_s2_dgrad_kernel<PREC, k.kstep, RAGGED>), grid, dim3(kThreads), 0, st, in, (const uint16_t*)wh, (const uint16_t*)wl,
+                         out, g.K, g.N, H, W, Ho, Wo, tiles_x);
+    }
+  }
+  return hipGetLastError();
+}
+
+// the bias gradient's chunks per plane: one per kBiasChunkPixels pixels, at most kBiasMaxChunks (Cout * chunks workgroups fill the device from 64
+// channels on); the partials are Cout * chunks doubles of the workspace
+constexpr int kBiasChunkPixels = 4096, kBiasMaxChunks = 64;
+inline int bias_grad_chunks(long long plane) {
+  const long long c = (plane + kBiasChunkPixels - 1) / kBiasChunkPixels;
+  return (int)(c < 1 ? 1 : c > kBiasMaxChunks ? kBiasMaxChunks : c);
+}
+
+// P = grad_y on the Ho x Wo grid, Q = x read at (2y - 1 + ky, 2x - 1 + kx); the split rule and the ordered reduce of every weight gradient here
+template <int PREC, bool RAGGED, bool SCALED>
+hipError_t launch_s2_wgrad_prec(const float* x, const float* grad_y, float* grad_w, float* grad_bias, void* workspace, const float* scale, int B,
+                                int Cin, int Cout, int H, int W, hipStream_t st) {
+  constexpr int RH = wgrad_rows(kOpConv3S2);
+  const int Ho = strided_out(H), Wo = strided_out(W);
+  const WgradSplit sp = wgrad_split(kOpConv3S2, B, Ho, Wo);
+  const int tiles_x = (Wo + 31) / 32, tiles_y = (Ho + RH - 1) / RH;
+  float* part = reinterpret_cast<float*>(workspace);
+  const dim3 grid((unsigned)(((Cin + 63) / 64) * ((Cout + 63) / 64)), (unsigned)sp.splits);
+  const size_t total = (size_t)Cin * Cout * 9;
+  const long long plane = (long long)Ho * Wo;
+  const int chunks = bias_grad_chunks(plane);
+  const long long per_chunk = (plane + chunks - 1) / chunks;
+  double* bias_part = reinterpret_cast<double*>(workspace);      // [Cout][chunks]
+  if constexpr (SCALED) {
+    hipLaunchKernelGGL((dd_conv_wgrad_scaled_kernel<PREC, 3, 2, 1, RH, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, Ho, Wo, H, W,
+                       tiles_x, tiles_y, (long long)sp.tiles, sp.tiles_per_split, scale);
+    hipLaunchKernelGGL(dd_conv_wgrad_reduce_scaled_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits,
+                       scale);
+    if (grad_bias) {      // (the reduce above has read the partial sums: the workspace is free again)
+      hipLaunchKernelGGL((dd_conv_bias_grad_scaled_kernel<PREC>), dim3((unsigned)Cout, (unsigned)chunks), dim3(kThreads), 0, st, grad_y, bias_part, B, Cout,
+                         plane, per_chunk, scale);
+      hipLaunchKernelGGL(dd_conv_bias_grad_reduce_scaled_kernel, dim3(blocks_for((size_t)Cout)), dim3(kThreads), 0, st, (const double*)bias_part, grad_bias,
+                         Cout, chunks, scale);
+    }
+  } else {
+    hipLaunchKernelGGL((dd_conv_wgrad_kernel<PREC, 3, 2, 1, RH, RAGGED>), grid, dim3(kThreads), 0, st, grad_y, x, part, Cout, Cin, Ho, Wo, H, W, tiles_x,
+                       tiles_y, (long long)sp.tiles, sp.tiles_per_split);
+    hipLaunchKernelGGL(dd_conv_wgrad_reduce_kernel, dim3(blocks_for(total)), dim3(kThreads), 0, st, (const float*)part, grad_w, total, sp.splits);
+    if (grad_bias) {
+      hipLaunchKernelGGL((dd_conv_bias_grad_kernel<PREC>), dim3((unsigned)Cout, (unsigned)chunks), dim3(kThreads), 0, st, grad_y, bias_part, B, Cout, plane,
+                         per_chunk);
+      hipLaunchKernelGGL(dd_conv_bias_grad_reduce_kernel, dim3(blocks_for((size_t)Cout)), dim3(kThreads), 0, st, (const double*)bias_part, grad_bias, Cout,
+                         chunks);
+    }
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
@@ -375,6 +469,41 @@ hipError_t launch_grad_scale(const float* grad_y, int64_t n, int prec, int amax_
   }
   hipLaunchKernelGGL(dd_conv_grad_scale_pair_kernel, dim3(1), dim3(1), 0, st, scale, amax_exp);
   return hipGetLastError();
+}
+
+// ---- 3x3 stride 2 ----------------------------------------------------------------------------------------------------------------------------------
+size_t workspace_bytes_s2(int B, int Cin, int Cout, int H, int W, int prec) {
+  const size_t fwd = packed_halfs(kOpConv3S2, 0, Cin, Cout), bwd = packed_halfs(kOpConv3S2, 1, Cin, Cout);
+  const size_t packed = (fwd > bwd ? fwd : bwd) * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
+  const size_t partials = (size_t)wgrad_split(kOpConv3S2, B, strided_out(H), strided_out(W)).splits * 9 * (size_t)Cin * (size_t)Cout * sizeof(float);
+  const size_t bias_part = (size_t)Cout * (size_t)bias_grad_chunks((long long)strided_out(H) * strided_out(W)) * sizeof(double);
+  size_t need = packed > partials ? packed : partials;
+  if (bias_part > need) need = bias_part;      // (the weight gradient's partials, at least 36 Cin bytes per output channel and split, are the larger)
+  return (need + 255) / 256 * 256;
+}
+
+hipError_t launch_conv_s2_forward(const float* x, const float* w, const float* bias, float* y, void* workspace, int B, int Cin, int Cout, int H, int W,
+                                  int prec, hipStream_t st) {
+  return dispatch(prec, Cin, Cout, false, [&](auto p, auto ragged, auto scaled) {
+    return launch_s2_prec<decltype(p)::value, decltype(ragged)::value, decltype(scaled)::value>(0, x, w, bias, y, workspace, nullptr, B, Cin, Cout, H,
+                                                                                                W, st);
+  });
+}
+
+hipError_t launch_conv_s2_dgrad(const float* grad_y, const float* w, float* grad_x, void* workspace, int B, int Cin, int Cout, int H, int W, int prec,
+                                hipStream_t st, const float* scale) {
+  return dispatch(prec, Cin, Cout, scale != nullptr, [&](auto p, auto ragged, auto scaled) {
+    return launch_s2_prec<decltype(p)::value, decltype(ragged)::value, decltype(scaled)::value>(1, grad_y, w, nullptr, grad_x, workspace, scale, B,
+                                                                                                Cin, Cout, H, W, st);
+  });
+}
+
+hipError_t launch_conv_s2_wgrad(const float* x, const float* grad_y, float* grad_w, float* grad_bias, void* workspace, int B, int Cin, int Cout, int H,
+                                int W, int prec, hipStream_t st, const float* scale) {
+  return dispatch(prec, Cin, Cout, scale != nullptr, [&](auto p, auto ragged, auto scaled) {
+    return launch_s2_wgrad_prec<decltype(p)::value, decltype(ragged)::value, decltype(scaled)::value>(x, grad_y, grad_w, grad_bias, workspace, scale,
+                                                                                                      B, Cin, Cout, H, W, st);
+  });
 }
 
 }  // namespace ddconv

@@ -1,11 +1,15 @@
-// dd_conv_kernels.h -- the GEMM kernels of csrc/dd_conv.hip, written ONCE and included there TWICE: with DD_CONV_SCALED 0 it defines the kernels of
-// include/ddepth_conv.h (dd_conv_igemm_kernel, dd_conv_wgrad_kernel, dd_conv1x1_gemm_kernel, dd_conv1x1_wgrad_kernel, dd_conv_wgrad_reduce_kernel), with
+// dd_conv_kernels.h -- the GEMM kernels of csrc/dd_conv.hip, written ONCE and included there TWICE (and a third time, DD_CONV_BIAS 1, for the biased
+// forward of include/ddepth_conv_strided.h alone: below): with DD_CONV_SCALED 0 it defines the kernels of include/ddepth_conv.h and ddepth_conv_strided.h
+// (dd_conv_igemm_kernel, dd_conv_wgrad_kernel, dd_conv1x1_gemm_kernel, dd_conv1x1_wgrad_kernel, dd_conv_wgrad_reduce_kernel, dd_conv_s2_dgrad_kernel,
+// dd_conv_bias_grad_kernel, dd_conv_bias_grad_reduce_kernel), with
 // DD_CONV_SCALED 1 their twins *_scaled_kernel of include/ddepth_conv_scaled.h, which take the device pair scale = {s, 1 / s} as one more (last)
 // argument, multiply every loaded value of grad_y by s before it is rounded to its 16-bit operand, and undo it with 1 / s where the result is stored:
 //   dd_conv_igemm / dd_conv1x1_gemm   `in` is grad_y (the twins are launched for the data gradients only); the accumulators times 1 / s in the epilogue
-//   dd_conv_wgrad                     grad_y is P for the 3x3 (S == 1) and Q for the transpose convolution (S == 2); the partials stay scaled
+//   dd_conv_wgrad                     grad_y is P for the 3x3 (KS == 3, either stride) and Q for the transpose convolution (KS == 2); the partials stay scaled
 //   dd_conv1x1_wgrad                  grad_y is Pm; the partials stay scaled
 //   dd_conv_wgrad_reduce              writes sum * 1 / s
+//   dd_conv_s2_dgrad                  the 3x3 stride-2 data gradient: `gy` is grad_y; the accumulators times 1 / s in the epilogue
+//   dd_conv_bias_grad                 the sum of the rounded grad_y * s, times 1 / s
 // Both factors are powers of two, and the order of every accumulation is untouched.  The preprocessor and not a template argument makes the
 // twins: a kernel's name and argument list are part of what a change may not touch (tools/code_object_diff.py); a template argument would
 // rename every instantiation, and a shared __device__ body inlined into two kernels does not compile to the instruction stream the kernel had.
@@ -15,11 +19,21 @@
 #define DD_CONV_SCALE_PARAM , const float* __restrict__ scale      /* the address is the same for every lane: scalar loads */
 #define DD_CONV_GY(is_grad_y, v) ((is_grad_y) ? (v) * scale[0] : (v))
 #define DD_CONV_UNSCALED(v) ((v) * scale[1])
+#define DD_CONV_BIASED(v, n) (v)
+#elif DD_CONV_BIAS
+// a third pass (include/ddepth_conv_strided.h): dd_conv_igemm_bias_kernel alone, the implicit GEMM with one more (last) argument bias[N] or NULL,
+// added in fp32 where the accumulator is stored.  Its own kernel for the reason the twins are: the argument list of dd_conv_igemm_kernel stays.
+#define DD_CONV_KERNEL(name) name##_bias_kernel
+#define DD_CONV_SCALE_PARAM , const float* __restrict__ bias
+#define DD_CONV_GY(is_grad_y, v) (v)
+#define DD_CONV_UNSCALED(v) (v)
+#define DD_CONV_BIASED(v, n) (bias ? (v) + bias[n] : (v))
 #else
 #define DD_CONV_KERNEL(name) name##_kernel
 #define DD_CONV_SCALE_PARAM
 #define DD_CONV_GY(is_grad_y, v) (v)
 #define DD_CONV_UNSCALED(v) (v)
+#define DD_CONV_BIASED(v, n) (v)
 #endif
 
 // ---- forward and data gradient --------------------------------------------------------------------------------------------------------------------
@@ -112,12 +126,13 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_igemm)(const 
         const size_t oy = 2 * (size_t)y + (t4 >> 1), ox = 2 * (size_t)x + (t4 & 1);
         out[(((size_t)b * cout + co) * (2 * (size_t)Ht) + oy) * (2 * (size_t)Wt) + ox] = acc[nb][r];
       } else {
-        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = DD_CONV_UNSCALED(acc[nb][r]);
+        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = DD_CONV_BIASED(DD_CONV_UNSCALED(acc[nb][r]), n);
       }
     }
   }
 }
 
+#if !DD_CONV_BIAS      // (the bias pass: the implicit GEMM alone)
 // ---- weight gradient --------------------------------------------------------------------------------------------------------------------------------
 // P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
 //   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_wgrad)(const 
         const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
         if (idx >= 64 * PP) break;
         uint16_t hi, lo;
-        to_operand<PREC>(DD_CONV_GY(S == 1, v[j]), hi, lo);      // (P is grad_y for the 3x3 ...
+        to_operand<PREC>(DD_CONV_GY(KS != 2, v[j]), hi, lo);      // (P is grad_y for the 3x3, stride 1 or 2, ...
         PL[0][ch * PCS + rem] = hi;
         if constexpr (PREC == kPrecF16x3) PL[NL - 1][ch * PCS + rem] = lo;
       }
@@ -184,7 +199,7 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_wgrad)(const 
         const int idx = base + j * kThreads, ch = idx / QP, rem = idx - ch * QP;
         if (idx >= 64 * QP) break;
         uint16_t hi, lo;
-        to_operand<PREC>(DD_CONV_GY(S == 2, v[j]), hi, lo);      // ... and Q for the transpose convolution)
+        to_operand<PREC>(DD_CONV_GY(KS == 2, v[j]), hi, lo);      // ... and Q for the transpose convolution)
         QL[0][ch * QCS + rem] = hi;
         if constexpr (PREC == kPrecF16x3) QL[NL - 1][ch * QCS + rem] = lo;
       }
@@ -413,7 +428,151 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_wgrad_reduce)
   grad_w[i] = DD_CONV_UNSCALED(s);
 }
 
+// ---- 3x3 stride 2 pad 1: data gradient (include/ddepth_conv_strided.h) --------------------------------------------------------------------------------
+// grad_x[ci][iy][ix] = sum over co, ky, kx of grad_y[co][(iy + 1 - ky) / 2][(ix + 1 - kx) / 2] . w[co][ci][ky][kx] where both quotients are whole and
+// inside the Ho x Wo grid.  Input pixel (2y + dy, 2x + dx) of the half-resolution grid (y, x) takes, per axis, the centre tap from grad_y row y when
+// dy = 0, and taps 2 and 0 from rows y and y + 1 when dy = 1: tap (ky, kx) belongs to the parity class dy = (ky != 1), dx = (kx != 1) and reads
+// grad_y at (y + (ky == 0), x + (kx == 0)).  One class has 1 tap, two have 2, one has 4 -- nine tap GEMMs per 2 x 2 input pixels, no product with an
+// inserted zero.  A workgroup owns a 4 x 32 tile of the half-resolution grid, 64 input channels and all four classes (eight accumulators); the
+// patch is (4 + 1) x (32 + 1) pixels of grad_y, KC output channels at a time, zero at row Ho / column Wo (the absent tap of an even H / W) and for
+// channels >= K.  gy [B][K][Ho][Wo], wp [9][N][K] with wp[ky * 3 + kx][ci][co] = w[co][ci][ky][kx] (pack mode kPackConvS2Bwd), out [B][N][H][W];
+// grid (tiles of the ceil(H / 2) x ceil(W / 2) grid, ceil(N / 64), B).  Pixels 2y + dy >= H or 2x + dx >= W are not stored; every other one is.
+template <int PREC, int KC, bool RAGGED>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_s2_dgrad)(const float* __restrict__ gy, const uint16_t* __restrict__ wh,
+                                                                    const uint16_t* __restrict__ wl, float* __restrict__ out, int K, int N,
+                                                                    int H, int W, int Ho, int Wo, int tiles_x DD_CONV_SCALE_PARAM) {
+  constexpr int PH = kTileH + 1, PW = kTileW + 1, PP = PH * PW;
+  constexpr int PS = KC + 8;      // halfs per patch pixel: a multiple of 8, so every 16-byte read is aligned
+  constexpr int NL = PREC == kPrecF16x3 ? 2 : 1;
+  __shared__ uint16_t patch[NL][PP * PS] __attribute__((aligned(16)));
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, l32 = lane & 31;
+  const int tx = blockIdx.x % tiles_x, ty = blockIdx.x / tiles_x, n0 = blockIdx.y * kTileN, b = blockIdx.z;
+  const int oy0 = ty * kTileH, ox0 = tx * kTileW;
+  const size_t plane = (size_t)Ho * Wo;
+  const float* gyb = gy + (size_t)b * K * plane;
+  const int Kp = RAGGED ? padded(K, KC) : K, Np = RAGGED ? padded(N, kTileN) : N;      // the weight image's row length and rows per tap
+
+  f32x16_t acc[4][2];      // [dy * 2 + dx][32-channel block]
+#pragma unroll
+  for (int c = 0; c < 4; ++c)
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { acc[c][0][i] = 0.0f; acc[c][1][i] = 0.0f; }
+
+  for (int kc = 0; kc < K; kc += KC) {
+    __syncthreads();      // the previous chunk's reads are over
+    for (int base = tid; base < KC * PP; base += kThreads * kFillBatch) {
+      float v[kFillBatch];
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP, pr = rem / PW, pc = rem - pr * PW;
+        const int oy = oy0 + pr, ox = ox0 + pc;
+        v[j] = 0.0f;
+        if (idx < KC * PP && (!RAGGED || kc + ch < K) && oy < Ho && ox < Wo) v[j] = gyb[(size_t)(kc + ch) * plane + (size_t)oy * Wo + ox];
+      }
+#pragma unroll
+      for (int j = 0; j < kFillBatch; ++j) {
+        const int idx = base + j * kThreads, ch = idx / PP, rem = idx - ch * PP;
+        if (idx >= KC * PP) break;
+        uint16_t hi, lo;
+        to_operand<PREC>(DD_CONV_GY(true, v[j]), hi, lo);
+        patch[0][rem * PS + ch] = hi;
+        if constexpr (PREC == kPrecF16x3) patch[NL - 1][rem * PS + ch] = lo;
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky) {
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        const int cls = (ky != 1 ? 2 : 0) + (kx != 1 ? 1 : 0);
+        const int pp = ((wave + (ky == 0 ? 1 : 0)) * PW + (l32 + (kx == 0 ? 1 : 0))) * PS + 8 * half;
+        const size_t wrow = ((size_t)(ky * 3 + kx) * Np + n0 + l32) * Kp + kc + 8 * half;
+#pragma unroll
+        for (int kk = 0; kk < KC; kk += 16) {
+          const uint4 bh = *reinterpret_cast<const uint4*>(&patch[0][pp + kk]);
+          uint4 bl = bh;
+          if constexpr (PREC == kPrecF16x3) bl = *reinterpret_cast<const uint4*>(&patch[NL - 1][pp + kk]);
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            const size_t wo = wrow + (size_t)nb * 32 * Kp + kk;
+            const uint4 ah = *reinterpret_cast<const uint4*>(wh + wo);
+            uint4 al = ah;
+            if constexpr (PREC == kPrecF16x3) al = *reinterpret_cast<const uint4*>(wl + wo);
+            acc[cls][nb] = mma_pair<PREC>(ah, al, bh, bl, acc[cls][nb]);
+          }
+        }
+      }
+    }
+  }
+
+  // accumulator entry r of lane l: column (half-resolution pixel) l % 32, row (input channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
+  const int y = oy0 + wave, x = ox0 + l32;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int iy = 2 * y + (c >> 1), ix = 2 * x + (c & 1);
+    if (iy >= H || ix >= W) continue;
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int n = n0 + nb * 32 + 8 * (r / 4) + 4 * half + (r % 4);
+        if constexpr (RAGGED) {
+          if (n >= N) continue;
+        }
+        out[(((size_t)b * N + n) * H + iy) * (size_t)W + ix] = DD_CONV_UNSCALED(acc[c][nb][r]);
+      }
+    }
+  }
+}
+
+// ---- bias gradient --------------------------------------------------------------------------------------------------------------------------------------
+// grad_bias[co] = sum over b, y, x of grad_y as the weight gradient sees it -- every element rounded to the operand (hi, plus lo in the split mode; the
+// scaled pass: of grad_y * s, the sum times 1 / s) -- so it is the weight gradient of an all-ones input plane.  Two launches, fp64 throughout: workgroup
+// (co, c) adds chunk c of every image's plane -- thread t the elements t, t + 256, ... of the chunk, image after image, then a tree over the 256 sums in
+// LDS -- into part[co][c]; one thread per channel then adds its `chunks` partials in order.  The chunking depends on the shape alone
+// (bias_grad_chunks): fixed order, no atomics, the same bits on every run.
+template <int PREC>
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_bias_grad)(const float* __restrict__ gy, double* __restrict__ part, int B, int C,
+                                                                     long long plane, long long per_chunk DD_CONV_SCALE_PARAM) {
+  __shared__ double sums[kThreads];
+  const int co = blockIdx.x, tid = threadIdx.x;
+  const long long begin = (long long)blockIdx.y * per_chunk, end = begin + per_chunk < plane ? begin + per_chunk : plane;
+  double s = 0.0;
+  for (int b = 0; b < B; ++b) {
+    const float* g = gy + ((size_t)b * C + co) * (size_t)plane;
+    for (long long i = begin + tid; i < end; i += kThreads) {
+      uint16_t hi, lo;
+      to_operand<PREC>(DD_CONV_GY(true, g[i]), hi, lo);
+      if constexpr (PREC == kPrecBf16) {
+        s += (double)__builtin_bit_cast(float, (uint32_t)hi << 16);
+      } else {
+        s += (double)(float)__builtin_bit_cast(_Float16, hi);
+        if constexpr (PREC == kPrecF16x3) s += (double)(float)__builtin_bit_cast(_Float16, lo);
+      }
+    }
+  }
+  sums[tid] = s;
+  __syncthreads();
+  for (int d = kThreads / 2; d >= 1; d >>= 1) {
+    if (tid < d) sums[tid] += sums[tid + d];
+    __syncthreads();
+  }
+  if (tid == 0) part[(size_t)co * gridDim.y + blockIdx.y] = sums[0];
+}
+
+__global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_bias_grad_reduce)(const double* __restrict__ part, float* __restrict__ grad_bias, int C,
+                                                                            int chunks DD_CONV_SCALE_PARAM) {
+  const int co = blockIdx.x * kThreads + threadIdx.x;
+  if (co >= C) return;
+  double s = part[(size_t)co * chunks];
+  for (int k = 1; k < chunks; ++k) s += part[(size_t)co * chunks + k];
+  grad_bias[co] = DD_CONV_UNSCALED((float)s);
+}
+#endif      // !DD_CONV_BIAS
+
 #undef DD_CONV_KERNEL
 #undef DD_CONV_SCALE_PARAM
 #undef DD_CONV_GY
 #undef DD_CONV_UNSCALED
+#undef DD_CONV_BIASED

@@ -3,15 +3,19 @@
 head_specify/inference_steps/num_train_timesteps).  The visual backbone stays in PyTorch-ROCm; a
 stem-less BasicBlock ResNet equivalent of the reference's mmbev_res18/50/101
 (reference src/model/backbone/mmbev_resnet.py:101-194, which needs mmdet) is provided so the whole
-model can run offline with random-init weights.
+model can run offline with random-init weights.  Opt-in (``args.backbone_backend="hip"`` /
+DDEPTH_BACKBONE_BACKEND=hip): the backbone's convolutions run in the library (conv.convert_hip_conv
+with ``channels="any", strided=True``); the default leaves the backbone as it is.
 """
 from __future__ import annotations
 
+import os
 from types import SimpleNamespace
 
 import torch
 from torch import nn
 
+from .conv import convert_hip_conv
 from .head import build_head
 
 
@@ -89,6 +93,15 @@ def resolve_backbone(args):
     return getattr(module, name)
 
 
+def resolve_backbone_backend(backbone_backend=None) -> str:
+    """``args.backbone_backend`` / the environment variable DDEPTH_BACKBONE_BACKEND: "torch" (default; empty or absent) or "hip" (the backbone's
+    convolutions run in the library, the stride-2 openings of every stage included)."""
+    choice = backbone_backend or os.environ.get("DDEPTH_BACKBONE_BACKEND") or "torch"
+    if choice not in ("torch", "hip"):
+        raise ValueError(f"backbone_backend must be 'torch' or 'hip' (got {choice!r})")
+    return choice
+
+
 class Diffusion_DCbase_Model(nn.Module):
     def __init__(self, args=None, depth_backbone=None, depth_head=None, **kwargs):
         """As the reference (diffusion_dcbase_model.py:28-91): ``depth_backbone`` / ``depth_head`` may be injected as built modules;
@@ -105,6 +118,17 @@ class Diffusion_DCbase_Model(nn.Module):
                                               inference_steps=getattr(self.args, "inference_steps", 20),
                                               num_train_timesteps=getattr(self.args, "num_train_timesteps", 1000), depth_feature_dim=16,
                                               loss_cfgs=[], init_cfg=None, precision=getattr(self.args, "precision", None)))
+        # Opt-in: the (resolved or injected) backbone's convolutions in the library -- 3x3 s1 through dd_convx_*, the 3x3 s2 openings of every
+        # stage (conv1, the biased downsample, the RGB one included) through dd_conv3x3s2_*.  Same parameter tensors, same state-dict keys.  With
+        # a precision the library does not run (fp32, f16r, None) nothing is converted, as in the heads.  The backbone's BatchNorms have no
+        # switch here: ``model.depth_backbone = convert_hip_batchnorm(model.depth_backbone)`` (batchnorm.py) serves them.
+        self.backbone_backend = resolve_backbone_backend(getattr(self.args, "backbone_backend", None))
+        if self.backbone_backend == "hip":
+            precision = getattr(self.args, "precision", None)
+            if precision is None:      # (the head resolved its own: profile / DDEPTH_PRECISION)
+                precision = getattr(getattr(self.depth_head, "model", None), "precision", None)
+            self.depth_backbone = convert_hip_conv(self.depth_backbone, precision, channels="any", strided=True,
+                                                   grad_autoscale=bool(getattr(self.depth_head, "conv_grad_autoscale", False)))
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125
