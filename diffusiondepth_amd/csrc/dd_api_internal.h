@@ -326,6 +326,7 @@ int device_buf(dd_handle_t h, DevBuf& dst, size_t bytes, const void* src = nullp
 int pack_images(dd_handle_t h, const float* w, int64_t numel, int kid, const int* slots, int n_slots, DevBuf* images, bool transposed, hipStream_t s);
 // dd_api_plans.cpp
 int check_common(dd_handle_t h, int B, int lh, int lw, int ch, int cw, bool need_schedule);
+bool denoiser_image_addressable(int lh, int lw, int ch, int cw);
 int lane_count(dd_handle_t h, int B, int precision);
 int check_split(dd_handle_t h, int precision, const char* who);
 int acquire_lane_stream(dd_handle_t h, int lane, hipStream_t caller);      // dd_api.cpp: creates h->lane_stream[lane] (probed for concurrency with `caller`)

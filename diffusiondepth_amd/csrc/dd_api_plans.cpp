@@ -1,6 +1,8 @@
 // dd_api_plans.cpp -- per-shape plans and the launch sequences (see dd_api_internal.h for the split of the C ABI).
 #include "dd_api_internal.h"
 
+#include <algorithm>
+
 namespace ddapi {
 
 // need_schedule: the T-step loop (and its backward) reads the DDIM tables; ONE epsilon-network evaluation does not
@@ -14,7 +16,17 @@ int check_common(dd_handle_t h, int B, int lh, int lw, int ch, int cw, bool need
     return h->fail(DD_ERR_INVALID_ARG, "DD_VARIANT_RES needs cond_h,cond_w == lat_h,lat_w (reference ...res.py:340 adds them elementwise)");
   if (h->variant == DD_VARIANT_SWIN && (ch <= 0 || cw <= 0)) return h->fail(DD_ERR_INVALID_ARG, "cond_h, cond_w must be positive");
   if ((long long)B * lh * lw * COND_C >= (1LL << 31) * 4) return h->fail(DD_ERR_INVALID_ARG, "tensor too large");
+  if (!denoiser_image_addressable(lh, lw, ch, cw))
+    return h->fail(DD_ERR_UNSUPPORTED, "one image's 256-channel fp32 map of " + std::to_string(std::max((long long)lh * lw, (long long)ch * cw)) +
+                   " pixels does not fit the 32-bit byte offsets of the convolution kernels' buffer addressing (at most 2^32 - 16 bytes per image and tensor)");
   return DD_OK;
+}
+
+// The largest per-image tensor a denoiser convolution reads or writes: 256 channels of fp32 (the condition map as the caller hands it over, y2 in
+// the split-f16 modes) at the larger of the latent and the condition size.  Pure: decides before anything is allocated.
+bool denoiser_image_addressable(int lh, int lw, int ch, int cw) {
+  const unsigned long long px = (unsigned long long)std::max((long long)lh * lw, (long long)ch * cw);
+  return px <= (1ull << 40) && conv_buffer_addressable(px * COND_C * 4ull);
 }
 
 // Concurrent lanes of ONE dd_denoise / dd_denoise_backward call (option "streams"): the same rule for the forward and the backward, so that a
@@ -531,3 +543,6 @@ void drain_layer_events(dd_handle_t h) {
 }
 
 }  // namespace ddapi
+
+// test hook (not part of include/ddepth.h): the size rule of the kernels' buffer addressing
+extern "C" int dd_debug_buffer_addressable(unsigned long long bytes) { return dd::conv_buffer_addressable(bytes) ? 1 : 0; }

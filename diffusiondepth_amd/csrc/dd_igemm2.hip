@@ -5,7 +5,7 @@
 // Structured as a software pipeline:
 //
 //   * weights never touch VGPRs: each (channel-chunk, tap-group) stage is copied global -> LDS with
-//     `global_load_lds_dwordx4` (LDS-DMA, 1 KiB per wave-instruction) into a 2-deep ring, issued one
+//     `buffer_load_dwordx4 ... lds` (LDS-DMA, 1 KiB per wave-instruction) into a 2-deep ring, issued one
 //     stage ahead of the MFMAs that consume it.  The DMA writes LDS linearly, so the bank-conflict
 //     swizzle is applied to the packed GLOBAL image on the host (cdna guide rule 21) and undone by
 //     the same XOR on the ds_read side.
@@ -23,6 +23,9 @@
 //   * the prologue is VALU-lean (rocprof PMC showed the first cut VALU-bound: 7.4k VALU vs 576 MFMA per
 //     wave in conv3): staging geometry is computed once per kernel, each thread keeps its slice of the
 //     GroupNorm table in registers, packing uses v_cvt_pk_{bf16,f16}_f32.
+//   * global addresses are buffer addresses (dd_gcn.h): one descriptor per (tensor, image), a 32-bit per-lane byte offset computed once per
+//     tile, and a scalar / immediate term per channel chunk, tile row, cout block or DMA piece -- no 64-bit per-lane address arithmetic
+//     around the MFMAs (conv2: 4.7 -> 3.6 non-MFMA VALU and 4.2 -> 2.4 SALU per MFMA, tools/isa_mix.py).
 //   * bf16 / f16 outputs are stored 16 B per lane: `v_permlane32_swap` pairs the two half-waves'
 //     4-cout quads into 8 consecutive couts (cdna guide T21).
 #include "dd_igemm2_cfg.h"
@@ -104,6 +107,8 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
   int b, y0, x0;
   const char *in_b, *cond_b, *y4_b;
   char* xout_b;
+  // one buffer descriptor per (tensor, image) (dd_gcn.h): every patch access below is descriptor + per-lane offset (set_tile_geometry) + scalar / immediate
+  dd_buf_t in_d, cond_d, y4_d, xout_d;
   auto set_tile_base = [&](int t) {
     tile = t;
     b = t / tiles_per_img;
@@ -119,6 +124,10 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
     cond_b = (C::PRO == PRO_GN_ADD) ? reinterpret_cast<const char*>(p.cond) + (size_t)b * h * w * C::CIN * IN_ESZ : nullptr;
     y4_b = (C::PRO == PRO_X) ? reinterpret_cast<const char*>(p.y4) + (size_t)b * h * w * LATENT_C * 4 : nullptr;
     xout_b = (C::PRO == PRO_X) ? reinterpret_cast<char*>(p.xout) + (size_t)b * h * w * LATENT_C * 4 : nullptr;
+    in_d = dd_make_buf(in_b, (unsigned long long)h * w * C::CIN * IN_ESZ);
+    cond_d = dd_make_buf(cond_b, (C::PRO == PRO_GN_ADD) ? (unsigned long long)h * w * C::CIN * IN_ESZ : 0ull);
+    y4_d = dd_make_buf(y4_b, (C::PRO == PRO_X) ? (unsigned long long)h * w * LATENT_C * 4 : 0ull);
+    xout_d = dd_make_buf(xout_b, (C::PRO == PRO_X) ? (unsigned long long)h * w * LATENT_C * 4 : 0ull);
   };
   set_tile_base(tile);
 
@@ -128,29 +137,37 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
   // `s_waitcnt vmcnt(0)` right after issuing it, which serialises DMA latency with the MFMAs.  hipcc does not count
   // asm VMEM ops, so every wait for the DMA below is explicit; VMEM loads retire in issue order, so hipcc's own
   // counted waits for the raw patch loads only become more conservative (cdna guide 5.7).
+  // Buffer form (dd_gcn.h): the descriptor spans the packed stages of this workgroup's cout splits; the per-lane offset is 16 * lane for every
+  // piece of every stage, the stage and the piece are a scalar offset.  Where the stage's KiB divide evenly among the waves (W_EVEN, compile
+  // time) a wave copies its NWPIECE KiB as CONSECUTIVE pieces: straight-line issue, no per-piece test, one M0 write per stage; otherwise piece c of wave `wave`
+  // is KiB c * WAVES + wave as before, behind its test.  Either way the LDS image of a stage is the packed image's bytes in order.
   const unsigned lds_base = DD_LDS_BASE(smem);
-  constexpr int NWPIECE = (C::W_BYTES / 1024 + C::WAVES - 1) / C::WAVES;      // 1-KiB DMA instructions per wave and stage
-  auto issue_weight_piece = [&](int s, int c) {
-    const int si = flip ? (s < C::NSTAGE ? s + C::NSTAGE : s - C::NSTAGE) : s;      // (DD_SPLIT_FLIP: the stage's place in the packed image)
-    const char* src = reinterpret_cast<const char*>(p.wpack) + ((size_t)nsplit * C::NSTAGE + si) * (size_t)C::W_BYTES + lane * 16;
-    const unsigned dst = lds_base + C::W_OFF + (s & (C::NWB - 1)) * C::W_BYTES;
-    const int kc = c * C::WAVES + wave;
-    if (kc < C::W_BYTES / 1024) {
-      const char* gsrc = src + (size_t)kc * 1024;
-      const unsigned ldst = __builtin_amdgcn_readfirstlane(dst + kc * 1024);
-      DD_LDS_DMA16(smem, gsrc, ldst);
-    }
-  };
+  constexpr int W_KIB = C::W_BYTES / 1024;
+  constexpr int NWPIECE = (W_KIB + C::WAVES - 1) / C::WAVES;      // 1-KiB DMA instructions per wave and stage
+  constexpr bool W_EVEN = W_KIB % C::WAVES == 0 && NWPIECE <= 4;
+  const dd_bufw_t w_d = dd_make_bufw(reinterpret_cast<const char*>(p.wpack) + (size_t)nsplit * C::NSTAGE * (size_t)C::W_BYTES, (unsigned long long)C::SPW * C::NSTAGE * C::W_BYTES);
+  const unsigned lane16 = lane * 16;
   auto issue_weights = [&](int s) {
+    const int si = flip ? (s < C::NSTAGE ? s + C::NSTAGE : s - C::NSTAGE) : s;      // (DD_SPLIT_FLIP: the stage's place in the packed image)
+    const unsigned src = (unsigned)si * C::W_BYTES;
+    const unsigned dst = lds_base + C::W_OFF + (s & (C::NWB - 1)) * C::W_BYTES;
+    if constexpr (W_EVEN) {
+      const unsigned first = wave * (NWPIECE * 1024);
+      dd_buf_lds_dma16<NWPIECE>(smem, w_d, lane16, __builtin_amdgcn_readfirstlane(src + first), __builtin_amdgcn_readfirstlane(dst + first));
+    } else {
 #pragma unroll
-    for (int c = 0; c < NWPIECE; ++c) issue_weight_piece(s, c);
+      for (int c = 0; c < NWPIECE; ++c) {
+        const int kc = c * C::WAVES + wave;
+        if (kc < W_KIB) dd_buf_lds_dma16<1>(smem, w_d, lane16, __builtin_amdgcn_readfirstlane(src + kc * 1024), __builtin_amdgcn_readfirstlane(dst + kc * 1024));
+      }
+    }
   };
 
   // ---- per-thread staging geometry: independent of the channel chunk, computed once ---------------------
   // item u of this thread = 16-B piece `jfix` of patch pixel pp(u); THREADS % PPP == 0 keeps jfix constant
   const int jfix = tid & (PPP - 1);
   int lds_off[NIT];            // byte offset of the (swizzled) piece inside a patch buffer
-  int pix_off[NIT];            // clamped global pixel index gy*w+gx
+  unsigned voff[NIT];          // byte offset of the item's piece at the (clamped) pixel inside the image's input tensor, channel chunk 0: the per-lane part of every patch access
   unsigned m_valid = 0, m_inside = 0, m_interior = 0;
   auto set_tile_geometry = [&]() {
     m_valid = 0; m_inside = 0; m_interior = 0;
@@ -167,7 +184,10 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
       if (inside && pr >= C::HALO && pr < C::HALO + C::TH && pc >= C::HALO && pc < C::HALO + C::TW) m_interior |= 1u << u;
       const int gyc = gy < 0 ? 0 : (gy >= h ? h - 1 : gy);
       const int gxc = gx < 0 ? 0 : (gx >= w ? w - 1 : gx);
-      pix_off[u] = gyc * w + gxc;
+      const unsigned pix = (unsigned)(gyc * w + gxc), lc = (unsigned)(jfix * EPP);      // lc: the piece's first channel inside a chunk
+      if constexpr (C::IN_NCHW) voff[u] = (lc * h * w + pix) * 4u;                        // plane lc of the NCHW fp32 tensor
+      else if constexpr (C::CIN >= ACT_CB) voff[u] = (((lc >> 5) * h * w + pix) * ACT_CB + (lc & (ACT_CB - 1))) * IN_ESZ;      // channel-blocked (dd_elem.h)
+      else voff[u] = (pix * C::CIN + lc) * IN_ESZ;                                       // 16-channel NHWC
       lds_off[u] = pp * ROWB + ((jfix << 4) ^ swz16<RPB, PPP>(pc));
     }
   };
@@ -178,35 +198,37 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
   uint4 raw[RD][NIT][NLD];
   uint4 aux[NIT][NLD];
   auto load_raw = [&](int chunk, int slot) {
-    const int cbase = chunk * CK + jfix * EPP;
-    const size_t off0 = (C::CIN >= ACT_CB) ? ((size_t)(cbase >> 5) * h * w * ACT_CB + (cbase & (ACT_CB - 1))) : (size_t)cbase;
+    // the chunk's first channel cb is wave-uniform: its term of the address is the scalar offset (a chunk never straddles a 32-channel block
+    // unevenly: CK is 16 or a multiple of 32, so (cb & 31) + (lc & 31) < 32)
+    static_assert(CK == 16 || CK % ACT_CB == 0, "channel chunk against the 32-channel blocks");
+    const unsigned cb = (unsigned)chunk * CK;
     if constexpr (C::IN_NCHW) {
       // the caller's NCHW fp32 tensor: channel c of this image is the plane at c * h * w; the piece's eight channels are eight 4-byte loads
       // (lanes 0, 2, 4, ... = consecutive pixels of plane cbase + i, the odd lanes of plane cbase + 8 + i: two runs of 128 contiguous bytes)
       static_assert(EPP == 8 && NLD == 2 && C::PRO == PRO_RAW, "fp32 source, eight channels per piece, no auxiliary tensor");
-      const size_t HW = (size_t)h * w;
+      const unsigned HW4 = (unsigned)h * w * 4u;
 #pragma unroll
       for (int u = 0; u < NIT; ++u) {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(in_b) + (size_t)cbase * HW + pix_off[u];
 #pragma unroll
         for (int q = 0; q < NLD; ++q)
-          raw[slot][u][q] = make_uint4(src[(4 * q + 0) * HW], src[(4 * q + 1) * HW], src[(4 * q + 2) * HW], src[(4 * q + 3) * HW]);
+          raw[slot][u][q] = make_uint4(dd_buf_load4(in_d, voff[u], (cb + 4 * q + 0) * HW4, 0), dd_buf_load4(in_d, voff[u], (cb + 4 * q + 1) * HW4, 0),
+                                       dd_buf_load4(in_d, voff[u], (cb + 4 * q + 2) * HW4, 0), dd_buf_load4(in_d, voff[u], (cb + 4 * q + 3) * HW4, 0));
       }
       DD_VMEM_LOADS_ISSUED(NIT * NLD * 4);
       return;
     }
+    const unsigned soff = (C::CIN >= ACT_CB) ? ((cb >> 5) * h * w * ACT_CB + (cb & (ACT_CB - 1))) * IN_ESZ : cb * IN_ESZ;
 #pragma unroll
     for (int u = 0; u < NIT; ++u) {
-      const size_t goff = (off0 + (size_t)pix_off[u] * C::PIXSTRIDE) * IN_ESZ;
 #pragma unroll
-      for (int q = 0; q < NLD; ++q) raw[slot][u][q] = *reinterpret_cast<const uint4*>(in_b + goff + q * 16);
+      for (int q = 0; q < NLD; ++q) raw[slot][u][q] = dd_buf_load16(in_d, voff[u], soff, q * 16);
       if constexpr (C::PRO == PRO_GN_ADD) {
 #pragma unroll
-        for (int q = 0; q < NLD; ++q) aux[u][q] = *reinterpret_cast<const uint4*>(cond_b + goff + q * 16);
+        for (int q = 0; q < NLD; ++q) aux[u][q] = dd_buf_load16(cond_d, voff[u], soff, q * 16);
       } else if constexpr (C::PRO == PRO_X) {
         if (have_norm) {
 #pragma unroll
-          for (int q = 0; q < NLD; ++q) aux[u][q] = *reinterpret_cast<const uint4*>(y4_b + goff + q * 16);
+          for (int q = 0; q < NLD; ++q) aux[u][q] = dd_buf_load16(y4_d, voff[u], soff, q * 16);
         }
       }
     }
@@ -244,7 +266,6 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
       *reinterpret_cast<uint4*>(smem + pbuf_off + lds_off[u]) = ((m_inside >> u) & 1u) ? raw[slot][u][0] : make_uint4(0u, 0u, 0u, 0u);
       return;
     }
-    const int c0 = (C::PRO == PRO_X) ? jfix * EPP : chunk * CK + jfix * EPP;
     float v[EPP];
     if ((m_inside >> u) & 1u) {
       if constexpr (C::PRO == PRO_X) {
@@ -264,10 +285,11 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
           }
         }
         if (have_norm && ((m_interior >> u) & 1u)) {
-          const size_t goff = ((size_t)pix_off[u] * LATENT_C + c0) * 4;
+          // (the state has the input's layout: the item's offset in x is its offset in xout)
 #pragma unroll
           for (int q = 0; q < NLD; ++q)
-            *reinterpret_cast<float4*>(xout_b + goff + q * 16) = make_float4(v[q * 4], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
+            dd_buf_store16(xout_d, voff[u], 0, q * 16, make_uint4(__builtin_bit_cast(uint32_t, v[q * 4]), __builtin_bit_cast(uint32_t, v[q * 4 + 1]),
+                                                                  __builtin_bit_cast(uint32_t, v[q * 4 + 2]), __builtin_bit_cast(uint32_t, v[q * 4 + 3])));
         }
       } else if constexpr (C::SPLIT) {
         // fp32 tensors in HBM: the piece's 8 channels are two 16-byte loads; the GroupNorm table already carries SPLIT_PSCALE, raw inputs
@@ -663,6 +685,14 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
     const int cs = p.out_cstride ? p.out_cstride : C::COUT;
     out_b = reinterpret_cast<char*>(p.out) + ((size_t)e_b * cs + p.out_coff) * h * w * C::OUT_ESZ;
   }
+  // output stores through one descriptor per image: the lane's offset (its pixel of tile row wave * WM, its cout quad / octet inside a 32-cout
+  // block) once per tile; the tile row m and the 32-cout block are a scalar offset, the place inside the block an immediate
+  constexpr int OPC = (C::COUT >= ACT_CB) ? ACT_CB : C::COUT;       // elements between pixels (dd_elem.h: channel-blocked, or 16-channel NHWC)
+  const dd_buf_t out_d = dd_make_buf(out_b, (unsigned long long)h * w * C::COUT * C::OUT_ESZ);
+  const unsigned out_v = (((unsigned)(e_y0 + wave * C::WM) * w + (unsigned)(e_x0 + li)) * OPC + (C::OUT_ESZ == 2 ? 8 : 4) * g) * C::OUT_ESZ;
+  const unsigned out_row = (unsigned)w * OPC * C::OUT_ESZ;
+  const unsigned out_blk = (C::COUT >= ACT_CB) ? (unsigned)h * w * ACT_CB * C::OUT_ESZ : 0u;
+  (void)out_d; (void)out_v; (void)out_row; (void)out_blk;
 #pragma unroll
   for (int m = 0; m < C::WM; ++m) {
     const int gy = e_y0 + wave * C::WM + m, gx = e_x0 + li;
@@ -783,8 +813,7 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
         for (int k = 0; k < 2; ++k) {
           const auto rx = __builtin_amdgcn_permlane32_swap(pk[2 * k].x, pk[2 * k + 1].x, false, false);
           const auto ry = __builtin_amdgcn_permlane32_swap(pk[2 * k].y, pk[2 * k + 1].y, false, false);
-          const int co = n0 + n * 32 + 16 * k + 8 * g;
-          if (pvalid) *reinterpret_cast<uint4*>(out_b + act_offset(C::COUT, h, w, 0, co, gy, gx) * 2) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
+          if (pvalid) dd_buf_store16(out_d, out_v, ((n0 >> 5) + n) * out_blk + m * out_row, 32 * k, make_uint4(rx[0], ry[0], rx[1], ry[1]));
         }
       }
       continue;
@@ -816,7 +845,8 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
               *reinterpret_cast<float4*>(reinterpret_cast<char*>(p.out) + ((size_t)e_b * 4 * h * w * COND_C +
                   act_offset(COND_C, 2 * h, 2 * w, 0, cc, 2 * gy + (par >> 1), 2 * gx + (par & 1))) * 4) = make_float4(v[0], v[1], v[2], v[3]);
             } else {
-              *reinterpret_cast<float4*>(out_b + act_offset(C::COUT, h, w, 0, co, gy, gx) * 4) = make_float4(v[0], v[1], v[2], v[3]);
+              dd_buf_store16(out_d, out_v, ((n0 >> 5) + n) * out_blk + m * out_row, 32 * q, make_uint4(__builtin_bit_cast(uint32_t, v[0]), __builtin_bit_cast(uint32_t, v[1]),
+                                                                                                       __builtin_bit_cast(uint32_t, v[2]), __builtin_bit_cast(uint32_t, v[3])));
             }
           }
         } else {
@@ -837,7 +867,7 @@ __global__ void __launch_bounds__(C::THREADS, C::MIN_WAVES_PER_SIMD) conv_igemm2
               *reinterpret_cast<uint4*>(reinterpret_cast<char*>(p.out) + ((size_t)e_b * 4 * h * w * COND_C +
                   act_offset(COND_C, 2 * h, 2 * w, 0, cc, 2 * gy + (par >> 1), 2 * gx + (par & 1))) * 2) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
             } else {
-              *reinterpret_cast<uint4*>(out_b + act_offset(C::COUT, h, w, 0, co, gy, gx) * 2) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
+              dd_buf_store16(out_d, out_v, ((n0 >> 5) + n) * out_blk + m * out_row, 32 * k, make_uint4(rx[0], ry[0], rx[1], ry[1]));
             }
           }
         }
@@ -897,6 +927,11 @@ static hipError_t launch_one2(const ConvParams& p, hipStream_t s) {
     if (e != hipSuccess) return e;
     attr_set = true;
   }
+  // buffer addressing: a per-image tensor this kernel cannot address is an error here, whatever route the launch took (the denoiser's entry
+  // points refuse such sizes before they allocate: check_common, dd_api_plans.cpp)
+  const unsigned long long px = (unsigned long long)p.h * (unsigned long long)p.w;
+  if (px > (1ull << 40) || !conv_buffer_addressable(px * C::CIN * C::IN_ESZ) || (!C::SCATTER && !conv_buffer_addressable(px * C::COUT * C::OUT_ESZ)))      // (the scatter store keeps its 64-bit addresses)
+    return hipErrorInvalidValue;
   unsigned n_wg = (unsigned)(p.tiles_x * p.tiles_y * p.B * (C::COUT_PAD / C::NT / C::SPW));
   dim3 grid(n_wg, 1);
   hipLaunchKernelGGL(conv_igemm2_kernel<C>, grid, dim3(C::THREADS), C::SMEM_BYTES, s, p);

@@ -81,6 +81,10 @@ enum Prologue : int {
 };
 
 // One 3x3 convolution launch of the fused path.
+// The fused convolutions address every per-image tensor through a buffer descriptor (dd_gcn.h): a 32-bit byte offset from the image's first
+// byte.  A tensor of `bytes` bytes per image is addressable when its last 16-byte access still begins below 2^32.
+constexpr bool conv_buffer_addressable(unsigned long long bytes) { return bytes <= (1ull << 32) - 16; }
+
 struct ConvParams {
   const void* in;           // producing layer's raw output (NHWC, activation element type); PRO_X: x (fp32)
   const void* wpack;        // packed weights (activation element type)
