@@ -308,24 +308,77 @@ def adaptive_avg_pool2d(x, out_h, out_w):
     return out
 
 
-def fpn_aggregate(fsd, fp, dtype=np.float64):
+def _conv_bn_relu(x, w, bn, quant, pad=0, transposed=False):
+    """Conv (bias-free) + BatchNorm(eval) + ReLU.  quant=None: the three modules one after the other, as the reference runs them.
+    quant=f: the operand-rounding emulation of a 16-bit kernel mode -- BatchNorm folded into the weights (per output channel) and a bias
+    first, as the library does, then f on the input tensor and on the folded weights, products accumulated in the arrays' own precision
+    (fp64 by default), the bias added unrounded."""
+    def conv(a, k):
+        # same values, taps outermost in memory: conv2d's per-tap slices k[:, :, dy, dx] are then contiguous matrices (BLAS instead of NumPy's
+        # strided fallback loop: 20x on the 3x3 fusion convolutions)
+        k = np.ascontiguousarray(k.transpose(2, 3, 0, 1)).transpose(2, 3, 0, 1)
+        return conv_transpose2d(a, k, None, stride=2, pad=0) if transposed else conv2d(a, k, None, stride=1, pad=pad)
+
+    if quant is None:
+        return relu(batch_norm_eval(conv(x, w), *bn))
+    gamma, beta, mean, var = bn
+    s = gamma / np.sqrt(var + BN_EPS)
+    wf = w * (s.reshape(1, -1, 1, 1) if transposed else s.reshape(-1, 1, 1, 1))      # ConvTranspose2d weights are (Ci, Co, kh, kw)
+    y = conv(np.asarray(quant(x), dtype=x.dtype), np.asarray(quant(wf), dtype=x.dtype))
+    return relu(y + (beta - mean * s).reshape(1, -1, 1, 1))
+
+
+def fpn_aggregate(fsd, fp, dtype=np.float64, quant=None):
     """Condition aggregation of DDIMDepthEstimate_Res.forward (reference src/model/head/ddim_depth_estimate_res.py:108-118):
     top-down over the pyramid, x = conv_lateral[i](f_i) [+ adaptive_avg_pool2d(conv_up[i](x_prev), size of x)], with
     conv_lateral = Conv3x3(bias=False)+BN(eval)+ReLU (...res.py:60-69) and conv_up = ConvTranspose2d(k2, s2, bias=False)
-    +BN(eval)+ReLU (...res.py:71-84).  fsd: state-dict entries "conv_lateral.*" / "conv_up.*"; fp: list of 4 NCHW maps."""
+    +BN(eval)+ReLU (...res.py:71-84).  fsd: state-dict entries "conv_lateral.*" / "conv_up.*"; fp: list of 4 NCHW maps.
+    quant (default None: the reference's arithmetic, unchanged): operand rounding of every convolution, see _conv_bn_relu."""
     sd = _cast_sd(fsd, dtype)
     n = len(fp)
     x = None
     for i in range(n):
         lvl = n - i - 1
         f = np.asarray(fp[lvl], dtype=dtype)
-        cur = relu(batch_norm_eval(conv2d(f, sd[f"conv_lateral.{lvl}.0.weight"]), *_bn_args(sd, f"conv_lateral.{lvl}.1")))
+        if quant is None:
+            cur = relu(batch_norm_eval(conv2d(f, sd[f"conv_lateral.{lvl}.0.weight"]), *_bn_args(sd, f"conv_lateral.{lvl}.1")))
+        else:
+            cur = _conv_bn_relu(f, sd[f"conv_lateral.{lvl}.0.weight"], _bn_args(sd, f"conv_lateral.{lvl}.1"), quant, pad=1)
         if i > 0:
-            up = conv_transpose2d(x, sd[f"conv_up.{lvl}.0.weight"], None, stride=2, pad=0)
-            up = relu(batch_norm_eval(up, *_bn_args(sd, f"conv_up.{lvl}.1")))
+            if quant is None:
+                up = conv_transpose2d(x, sd[f"conv_up.{lvl}.0.weight"], None, stride=2, pad=0)
+                up = relu(batch_norm_eval(up, *_bn_args(sd, f"conv_up.{lvl}.1")))
+            else:
+                up = _conv_bn_relu(x, sd[f"conv_up.{lvl}.0.weight"], _bn_args(sd, f"conv_up.{lvl}.1"), quant, transposed=True)
             cur = cur + adaptive_avg_pool2d(up, cur.shape[2], cur.shape[3])
         x = cur
     return x
+
+
+def hahi_neck(hsd, fp, dtype=np.float64, quant=None, prefix="hahineck."):
+    """HAHIHeteroNeck.forward with cross_att = self_att = False, as every DiffusionDepth head builds it (reference
+    src/model/necks/hahi.py:170-173,196-197,226-272; mmcv ConvModule = Conv2d(bias=False) + BN(eval) + ReLU):
+        l_i   = lateral_convs[i](x_i)                                   1x1, C_i -> C_i
+        e_0   = conv_proj(l_0),  e_i = trans_proj[i-1](l_i)             1x1, C_i -> 512
+        out_0 = conv_fusion(cat[e_0, l_0])                              3x3, 512 + C_0 -> C_0          (hahi.py:249)
+        out_i = trans_fusion[i-1](cat[l_i, e_i])                        3x3, C_i + 512 -> C_i          (hahi.py:262)
+    hsd: the keys of synth.make_hahi_state_dict (below ``prefix``); fp: list of NCHW maps, finest first.  Returns the list of out_i.
+    quant: operand rounding of every convolution, see _conv_bn_relu."""
+    sd = _cast_sd({k[len(prefix):]: v for k, v in hsd.items() if k.startswith(prefix)}, dtype)
+
+    def cm(name, x, pad=0):
+        return _conv_bn_relu(x, sd[name + ".conv.weight"], _bn_args(sd, name + ".bn"), quant, pad=pad)
+
+    outs = []
+    for i, f in enumerate(fp):
+        lat = cm(f"lateral_convs.{i}", np.asarray(f, dtype=dtype))
+        if i == 0:
+            emb = cm("conv_proj.0", lat)
+            outs.append(cm("conv_fusion.0", np.concatenate([emb, lat], axis=1), pad=1))
+        else:
+            emb = cm(f"trans_proj.{i - 1}", lat)
+            outs.append(cm(f"trans_fusion.{i - 1}", np.concatenate([lat, emb], axis=1), pad=1))
+    return outs
 
 
 def head_hot_path(sd, gt_depth, cond, x_T, noise, timesteps, T=20, variant="res", dtype=np.float64):

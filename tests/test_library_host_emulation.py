@@ -578,6 +578,11 @@ def test_hahi_neck_on_the_split_f16_kernels(lib):
     ref32 = be.condition(fp, "fp32", neck=True)
     assert np.array_equal(b, ref32)                                # without the switch: the fp32 mode's kernels
     assert not np.array_equal(a, b) and maxabs(a, b) < 2e-5 * np.abs(b).max(), (maxabs(a, b), np.abs(b).max())
+    # ... and the fp32 kernels against the fp64 oracle of the neck, under the bound of its own fp32 evaluation (tests/neck_cases.py)
+    import neck_cases as NC
+    ref = O.fpn_aggregate(fpn, O.hahi_neck(nk, fp))
+    e32 = O.fpn_aggregate(fpn, O.hahi_neck(nk, fp, dtype=np.float32), dtype=np.float32).astype(np.float64) - ref
+    NC.assert_cond_close(ref32, ref, e32, "fp32")
     be.close()
 
 
