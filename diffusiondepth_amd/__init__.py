@@ -22,7 +22,7 @@ from .head import (DDIMDepthEstimate_Res, DDIMDepthEstimate_Swin_ADD, DDIMDepthE
                    DDIMDepthEstimate_ResVis, DDIMDepthEstimate_Swin_ADDHAHIVis)
 from .necks import HAHIHeteroNeck
 from .nlspn import NLSPN
-from .model import Diffusion_DCbase_Model
+from .model import Diffusion_DCbase_Model, fuse_basic_block_tails
 from .metric import Diffusion_DCbase_Metric, MetricAccumulator
 from .loss import Diffusion_DCbase_Loss
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
@@ -35,7 +35,7 @@ __all__ = [
     "DDIMDepthEstimate_Res", "DDIMDepthEstimate_Swin_ADD", "DDIMDepthEstimate_Swin_ADDHAHI", "DDIMDepthEstimate_MPVIT_ADDHAHI",
     "DDIMDepthEstimate_ResVis", "DDIMDepthEstimate_Swin_ADDHAHIVis", "HAHIHeteroNeck", "NLSPN", "Diffusion_DCbase_Model",
     "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
-    "HipBatchNorm2d", "convert_hip_batchnorm", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
+    "HipBatchNorm2d", "convert_hip_batchnorm", "fuse_basic_block_tails", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
     "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec",
 ]
 __version__ = "0.1.0"

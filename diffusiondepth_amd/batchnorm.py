@@ -11,6 +11,11 @@ both the single-rank and the data-parallel case.
 
     convert_hip_batchnorm(head)            # or: DDIMDepthEstimate_Res(..., bn_backend="hip") / DDEPTH_BN_BACKEND=hip
 
+Where a residual joins, ``HipBatchNorm2d.forward(x, addend)`` runs the add inside the apply kernel (include/ddepth_bn_add.h): ``add_mode="pre"``
+is act(bn(x) + addend), the tail of a ResNet BasicBlock (model.fuse_basic_block_tails), ``"post"`` is act(bn(x)) + addend, the top-down add of the
+FPN (``bn_backend="hip+add"``).  The statistics are those of x alone, so the exchange is unchanged; the "pre" backward reads its mask from the
+output it kept and writes the addend's gradient in the pass that forms the sums.
+
 The library path needs contiguous fp32 tensors on a HIP device in .train() with tracked running statistics and a fixed momentum; anything
 else (eval mode, CPU tensors, other dtypes or layouts, ``momentum=None``, ``track_running_stats=False``) takes the torch path the module
 inherits and applies the activation behind it.  Nothing is copied or converted silently, and there is no CPU library path.
@@ -34,8 +39,13 @@ from . import dist as ddist
 ABI_SYMBOLS = ["dd_bn_last_error", "dd_bn_workspace_bytes", "dd_bn_stats", "dd_bn_finalize", "dd_bn_apply", "dd_bn_backward_reduce",
                "dd_bn_backward_apply"]
 
+# every symbol include/ddepth_bn_add.h declares (checked by tests/test_bn_add_cpu.py)
+ADD_ABI_SYMBOLS = ["dd_bn_apply_add", "dd_bn_backward_reduce_add"]
+
 ACT_NONE, ACT_RELU, ACT_LEAKY_RELU = 0, 1, 2      # dd_bn_act
 ACTIVATIONS = {None: ACT_NONE, "relu": ACT_RELU, "leaky_relu": ACT_LEAKY_RELU}
+ADD_PRE, ADD_POST = 0, 1                          # dd_bn_add_mode
+ADD_MODES = {"pre": ADD_PRE, "post": ADD_POST}
 
 _bound = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
@@ -56,6 +66,9 @@ def _lib():
         lib.dd_bn_backward_reduce.argtypes = [c_vp] * 5 + [c_int, c_f, c_vp, c_vp] + [c_int] * 3 + [c_vp]
         lib.dd_bn_backward_apply.restype = c_int
         lib.dd_bn_backward_apply.argtypes = [c_vp] * 8 + [c_int, c_f] + [c_int] * 3 + [c_vp]
+        lib.dd_bn_apply_add.restype, lib.dd_bn_apply_add.argtypes = c_int, [c_vp] * 6 + [c_int, c_f, c_int] + [c_int] * 3 + [c_vp]
+        lib.dd_bn_backward_reduce_add.restype = c_int
+        lib.dd_bn_backward_reduce_add.argtypes = [c_vp] * 4 + [c_int, c_f, c_vp, c_vp, c_vp] + [c_int] * 3 + [c_vp]
         _bound = lib
     return _bound
 
@@ -158,6 +171,37 @@ def bn_backward_apply(x, grad_y, mean_invstd, sums2, sums, weight=None, bias=Non
     return grad_x
 
 
+def bn_apply_add(x, mean_invstd, addend, weight=None, bias=None, act: int = ACT_NONE, slope: float = 0.0, add_mode: int = ADD_PRE) -> torch.Tensor:
+    """y = act(z + addend) (ADD_PRE) or act(z) + addend (ADD_POST), z = (x - mean) * invstd * weight + bias (dd_bn_apply_add)."""
+    _check_native(x, "x")
+    _check_native(addend, "addend")
+    if addend.shape != x.shape or addend.device != x.device:
+        raise RuntimeError(f"addend must have x's shape and device (got {tuple(addend.shape)} on {addend.device}, x {tuple(x.shape)} on {x.device})")
+    B, C, HW = _geometry(x)
+    y = torch.empty_like(x)
+    with torch.cuda.device(x.device):
+        _ck(_lib().dd_bn_apply_add(x.data_ptr(), mean_invstd.data_ptr(), _ptr(weight), _ptr(bias), addend.data_ptr(), y.data_ptr(), int(act),
+                                   float(slope), int(add_mode), B, C, HW, _stream(x)), "dd_bn_apply_add")
+    return y
+
+
+def bn_backward_reduce_add(x, grad_y, y, mean_invstd, act: int = ACT_NONE, slope: float = 0.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(g, sums2) of the ADD_PRE backward in one pass (dd_bn_backward_reduce_add): g = grad_y * act'(y), masked by the forward's output -- the
+    addend's gradient and the ``grad_y`` of ``bn_backward_apply(x, g, ..., act=ACT_NONE)`` -- and (2C) fp64 [sum g | sum g * xhat]."""
+    for name, t in (("x", x), ("grad_y", grad_y), ("y", y)):
+        _check_native(t, name)
+        if t.shape != x.shape:
+            raise RuntimeError(f"{name} must have x's shape (got {tuple(t.shape)}, x {tuple(x.shape)})")
+    B, C, HW = _geometry(x)
+    g = torch.empty_like(x)
+    sums2 = torch.empty(2 * C, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        ws = workspace_for(x, B, C, HW)
+        _ck(_lib().dd_bn_backward_reduce_add(x.data_ptr(), grad_y.data_ptr(), y.data_ptr(), mean_invstd.data_ptr(), int(act), float(slope),
+                                             g.data_ptr(), sums2.data_ptr(), ws.data_ptr(), B, C, HW, _stream(x)), "dd_bn_backward_reduce_add")
+    return g, sums2
+
+
 def _touch(t: Optional[torch.Tensor]):
     """The library wrote through the raw pointer: tell torch (the version counter is what HipBound's staleness check reads)."""
     if t is not None:
@@ -212,6 +256,72 @@ class BatchNormTrainFunction(Function):
         return gx, gw, gb, None, None, None, None, None, None, None
 
 
+class BatchNormAddTrainFunction(Function):
+    """(x, addend, weight, bias) -> act(batch_norm(x) + addend) (``add_mode`` ADD_PRE: a BasicBlock's tail) or act(batch_norm(x)) + addend
+    (ADD_POST: the FPN's top-down add), over include/ddepth_bn.h and include/ddepth_bn_add.h.  The statistics are those of x alone, so
+    ``exchange`` works as in BatchNormTrainFunction.  Kept for the backward: ADD_PRE x, the output y (its sign is the activation's mask),
+    mean_invstd, sums and weight; ADD_POST what BatchNormTrainFunction keeps.  The addend is never kept.  Nothing synchronises the host."""
+
+    @staticmethod
+    def forward(ctx, x, addend, weight, bias, running_mean, running_var, eps, momentum, act, slope, add_mode, exchange):
+        _check_native(x, "x")
+        _check_native(addend, "addend")
+        for name, p in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if p is not None:
+                _check_native(p, name)
+        if add_mode not in (ADD_PRE, ADD_POST):
+            raise ValueError(f"add_mode must be ADD_PRE or ADD_POST (got {add_mode!r})")
+        if add_mode == ADD_PRE and act == ACT_LEAKY_RELU and slope < 0:
+            raise RuntimeError("ADD_PRE with a LeakyReLU of negative slope: the output's sign is not the mask (HipBatchNorm2d takes the torch path)")
+        w = weight.detach() if weight is not None else None
+        b = bias.detach() if bias is not None else None
+        sums = bn_stats(x)
+        if exchange is not None:
+            tdist.all_reduce(sums, group=exchange[0])
+        mean_invstd = bn_finalize(sums, eps, momentum, running_mean, running_var)
+        _touch(running_mean)
+        _touch(running_var)
+        y = bn_apply_add(x, mean_invstd, addend.detach(), w, b, act, slope, add_mode)
+        if add_mode == ADD_PRE:
+            ctx.save_for_backward(x, y, mean_invstd, sums, weight)
+        else:
+            ctx.save_for_backward(x, mean_invstd, sums, weight, bias)
+        ctx.conf = (int(act), float(slope), int(add_mode), exchange)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        act, slope, add_mode, exchange = ctx.conf
+        need_x, need_r, need_w, need_b = ctx.needs_input_grad[:4]
+        none8 = (None,) * 8
+        if not (need_x or need_r or need_w or need_b):
+            return (None,) * 12
+        gy = grad_y.detach()
+        if gy.dtype != torch.float32 or not gy.is_contiguous():
+            gy = gy.float().contiguous()
+        if add_mode == ADD_PRE:
+            x, y, mean_invstd, sums, weight = ctx.saved_tensors
+            g, sums2 = bn_backward_reduce_add(x, gy, y, mean_invstd, act, slope)
+            gr, bias, act = g, None, ACT_NONE      # the data gradient is the plain BatchNorm backward of g
+        else:
+            x, mean_invstd, sums, weight, bias = ctx.saved_tensors
+            g, gr = gy, grad_y                     # the add sits behind the activation: its gradient is grad_y itself
+            if not (need_x or need_w or need_b):
+                return (None, gr) + (None,) * 10
+            sums2 = bn_backward_reduce(x, gy, mean_invstd, weight, bias, act, slope)
+        C = mean_invstd.numel() // 2
+        # the LOCAL sums are the parameter gradients, taken before the exchange (as in BatchNormTrainFunction)
+        gb = sums2[:C].to(torch.float32) if need_b else None
+        gw = sums2[C:].to(weight.dtype) if need_w else None
+        gx = None
+        if need_x:
+            if exchange is not None:
+                tdist.all_reduce(sums2, group=exchange[0])
+            gx = bn_backward_apply(x, g, mean_invstd, sums2, sums, weight, bias, act, slope)
+        return (gx, gr if need_r else None, gw, gb) + none8
+
+
 class HipBatchNorm2d(ddist.SyncBatchNorm):
     """``nn.BatchNorm2d`` (same parameters, buffers and state-dict keys) whose .train() forward and backward on a HIP device run in
     csrc/dd_bn.hip, with ``activation`` (None, "relu" or "leaky_relu" with ``negative_slope``) fused behind it.
@@ -227,6 +337,7 @@ class HipBatchNorm2d(ddist.SyncBatchNorm):
             raise ValueError(f"activation must be one of {list(ACTIVATIONS)} (got {activation!r})")
         self.activation = activation
         self.negative_slope = float(negative_slope)
+        self.add_mode = "pre"      # where forward(x, addend) adds: "pre" act(bn(x) + addend), "post" act(bn(x)) + addend
 
     def extra_repr(self):
         s = super().extra_repr()
@@ -249,15 +360,31 @@ class HipBatchNorm2d(ddist.SyncBatchNorm):
         return bool(self.training and self.track_running_stats and self.momentum is not None and x.is_cuda and x.dtype == torch.float32
                     and x.is_contiguous() and (self.weight is None or self.weight.dtype == torch.float32))
 
-    def forward(self, x):
+    def _native_addend(self, x, addend) -> bool:
+        """The library's apply takes this addend: a contiguous fp32 tensor of x's shape on x's device, and in "pre" mode an activation whose
+        output carries its own mask (any but a LeakyReLU of negative slope)."""
+        return bool(addend.is_cuda and addend.device == x.device and addend.dtype == torch.float32 and addend.is_contiguous()
+                    and addend.shape == x.shape
+                    and not (self.add_mode == "pre" and self.activation == "leaky_relu" and self.negative_slope < 0))
+
+    def forward(self, x, addend=None):
         self._check_input_dim(x)
-        if not self._native(x):
-            return self._activate(super().forward(x))
+        if addend is not None and self.add_mode not in ADD_MODES:
+            raise ValueError(f"add_mode must be one of {list(ADD_MODES)} (got {self.add_mode!r})")
+        if not self._native(x) or (addend is not None and not self._native_addend(x, addend)):
+            if addend is None:
+                return self._activate(super().forward(x))
+            z = super().forward(x)
+            return self._activate(z) + addend if self.add_mode == "post" else self._activate(z + addend)
         exchange = (self.process_group,) if self._exchanges() else None
         if exchange is None and x.numel() // x.shape[1] == 1:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
         if self.num_batches_tracked is not None:
             self.num_batches_tracked.add_(1)
+        if addend is not None:
+            return BatchNormAddTrainFunction.apply(x, addend, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
+                                                   self.momentum, ACTIVATIONS[self.activation], self.negative_slope, ADD_MODES[self.add_mode],
+                                                   exchange)
         return BatchNormTrainFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
                                             ACTIVATIONS[self.activation], self.negative_slope, exchange)
 
@@ -300,9 +427,10 @@ def convert_hip_batchnorm(module: nn.Module, process_group=None, fuse_activation
 
 
 def resolve_bn_backend(bn_backend: Optional[str] = None) -> str:
-    """The head keyword ``bn_backend`` / the environment variable DDEPTH_BN_BACKEND: "torch" (default; empty or absent) or "hip"."""
+    """The head keyword ``bn_backend`` / the environment variable DDEPTH_BN_BACKEND: "torch" (default; empty or absent), "hip", or "hip+add"
+    ("hip", and the FPN's top-down add runs inside the lateral BatchNorm's apply)."""
     import os
     choice = bn_backend or os.environ.get("DDEPTH_BN_BACKEND") or "torch"
-    if choice not in ("torch", "hip"):
-        raise ValueError(f"bn_backend must be 'torch' or 'hip' (got {choice!r})")
+    if choice not in ("torch", "hip", "hip+add"):
+        raise ValueError(f"bn_backend must be 'torch', 'hip' or 'hip+add' (got {choice!r})")
     return choice

@@ -1,6 +1,7 @@
-// dd_api_bn.cpp -- the C ABI of include/ddepth_bn.h: argument checks and the launch sequence; the kernels are in dd_bn.hip.
+// dd_api_bn.cpp -- the C ABI of include/ddepth_bn.h and include/ddepth_bn_add.h: argument checks and the launch sequence; the kernels are in dd_bn.hip.
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_bn.h"
+#include "../../include/ddepth_bn_add.h"
 #include "dd_bn.h"
 #include "dd_status.h"
 
@@ -81,6 +82,33 @@ int dd_bn_backward_apply(const float* x, const float* grad_y, const float* mean_
   if (int rc = check_shape(B, C, HW)) return rc;
   if (int rc = check_act(act, slope)) return rc;
   DD_STATUS_HIP(g_bn_err, ddbn::launch_backward_apply(x, grad_y, mean_invstd, weight, bias, sums2, sums, grad_x, act, slope, B, C, HW, (hipStream_t)stream));
+  return DD_OK;
+}
+
+// ---- include/ddepth_bn_add.h ---------------------------------------------------------------------------------------------------------------
+int dd_bn_apply_add(const float* x, const float* mean_invstd, const float* weight, const float* bias, const float* addend, float* y,
+                    int act, float slope, int add_mode, int B, int C, int HW, void* stream) {
+  if (!x || !mean_invstd || !addend || !y) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (y == x || y == addend) return g_bn_err.fail(DD_ERR_INVALID_ARG, "y may not alias x or addend");
+  if (add_mode != DD_BN_ADD_PRE && add_mode != DD_BN_ADD_POST)
+    return g_bn_err.fail(DD_ERR_INVALID_ARG, "add_mode must be a dd_bn_add_mode value (got %d)", add_mode);
+  if (int rc = check_shape(B, C, HW)) return rc;
+  if (int rc = check_act(act, slope)) return rc;
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_apply_add(x, mean_invstd, weight, bias, addend, y, act, slope, add_mode == DD_BN_ADD_POST, B, C, HW,
+                                                 (hipStream_t)stream));
+  return DD_OK;
+}
+
+int dd_bn_backward_reduce_add(const float* x, const float* grad_y, const float* y, const float* mean_invstd, int act, float slope,
+                              float* g, double* sums2, void* workspace, int B, int C, int HW, void* stream) {
+  if (!x || !grad_y || !y || !mean_invstd || !g || !sums2 || !workspace) return g_bn_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  if (g == x || g == grad_y || g == y) return g_bn_err.fail(DD_ERR_INVALID_ARG, "g may not alias x, grad_y or y");
+  if (int rc = check_shape(B, C, HW)) return rc;
+  if (int rc = check_act(act, slope)) return rc;
+  if (act == DD_BN_ACT_LEAKY_RELU && slope < 0.0f)
+    return g_bn_err.fail(DD_ERR_UNSUPPORTED, "LeakyReLU with a negative slope (%g): the sign of y is not the sign of z + r", (double)slope);
+  DD_STATUS_HIP(g_bn_err, ddbn::launch_backward_reduce_add(x, grad_y, y, mean_invstd, act, slope, g, sums2, workspace, B, C, HW,
+                                                           (hipStream_t)stream));
   return DD_OK;
 }
 

@@ -28,5 +28,10 @@ hipError_t launch_backward_reduce(const float* x, const float* grad_y, const flo
 hipError_t launch_backward_apply(const float* x, const float* grad_y, const float* mean_invstd, const float* weight, const float* bias,
                                  const double* sums2, const double* sums, float* grad_x, int act, float slope, int B, int C, int hw,
                                  hipStream_t st);
+// include/ddepth_bn_add.h: the apply with an addend (post != 0: behind the activation) and the PRE mode's one-pass backward reduction
+hipError_t launch_apply_add(const float* x, const float* mean_invstd, const float* weight, const float* bias, const float* addend, float* y,
+                            int act, float slope, int post, int B, int C, int hw, hipStream_t st);
+hipError_t launch_backward_reduce_add(const float* x, const float* grad_y, const float* y, const float* mean_invstd, int act, float slope,
+                                      float* g, double* sums2, void* workspace, int B, int C, int hw, hipStream_t st);
 
 }  // namespace ddbn

@@ -1,5 +1,5 @@
 // dd_bn.hip -- batch-statistics BatchNorm2d with a fused activation, forward and backward, as bandwidth-bound HIP kernels for gfx950
-// (include/ddepth_bn.h).  Tensors are contiguous fp32 NCHW: channel c of image b is the PLANE (b * C + c) of HW values.
+// (include/ddepth_bn.h), and the apply with a fused addend and its one-pass backward reduction (include/ddepth_bn_add.h).  Tensors are contiguous fp32 NCHW: channel c of image b is the PLANE (b * C + c) of HW values.
 //
 // Structure:
 //   grid (G, C, B): the G workgroups of a plane (256 threads each) stride over it with 16-byte loads and stores; a scalar head / tail covers
@@ -63,6 +63,18 @@ __device__ __forceinline__ Span make_span(const void* a, const void* b, const vo
   s.nvec = (n - s.head) >> 2;
   s.nscalar = n - 4 * s.nvec;
   return s;
+}
+
+// the same cut for a kernel of four tensors (dd_bn_backward_reduce_add_kernel)
+__device__ __forceinline__ Span make_span(const void* a, const void* b, const void* c, const void* d, int n) {
+  if ((((unsigned long long)a) & 15) != (((unsigned long long)d) & 15)) {
+    Span s;
+    s.head = n;
+    s.nvec = 0;
+    s.nscalar = n;
+    return s;
+  }
+  return make_span(a, b, c, n);
 }
 
 // index of the j-th scalar value (j < nscalar): the head first, then the tail behind the vectors.  Always < n.
@@ -290,6 +302,107 @@ __global__ __launch_bounds__(kThreads) void dd_bn_backward_apply_kernel(const fl
   }
 }
 
+// ---- the apply with an addend, and the one-pass backward reduction of its PRE mode (include/ddepth_bn_add.h) -------------------------------------
+// one fp32 add, never contracted into the LeakyReLU's multiply: POST-mode y is dd_bn_apply's y plus r, bit for bit
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// post: act(z) + r (the FPN's top-down add), else act(z + r) (a BasicBlock's tail); z is preact(), as everywhere
+__device__ __forceinline__ float apply_add_value(float x, float r, const PlaneConst& k, int act, float slope, bool post) {
+  const float z = preact(x, k);
+  return post ? add_rn(act_forward(z, act, slope), r) : act_forward(add_rn(z, r), act, slope);
+}
+
+__global__ __launch_bounds__(kThreads) void dd_bn_apply_add_kernel(const float* __restrict__ x, const float* __restrict__ mean_invstd,
+                                                                   const float* __restrict__ weight, const float* __restrict__ bias,
+                                                                   const float* __restrict__ addend, float* __restrict__ y, int act,
+                                                                   float slope, int post, int C, int hw) {
+  const int c = blockIdx.y;
+  const PlaneConst k = plane_const(mean_invstd, weight, bias, C, c);
+  const bool po = post != 0;
+  const size_t base = ((size_t)blockIdx.z * C + c) * (size_t)hw;
+  const float* p = x + base;
+  const float* q = addend + base;
+  float* o = y + base;
+  const Span s = make_span(p, q, o, hw);
+  const int tid = blockIdx.x * kThreads + threadIdx.x, stride = gridDim.x * kThreads;
+  const float4* vp = reinterpret_cast<const float4*>(p + s.head);
+  const float4* vq = reinterpret_cast<const float4*>(q + s.head);
+  float4* vo = reinterpret_cast<float4*>(o + s.head);
+  for (int i = tid; i < s.nvec; i += stride) {
+    const float4 a = vp[i], r = vq[i];
+    float4 v;
+    v.x = apply_add_value(a.x, r.x, k, act, slope, po);
+    v.y = apply_add_value(a.y, r.y, k, act, slope, po);
+    v.z = apply_add_value(a.z, r.z, k, act, slope, po);
+    v.w = apply_add_value(a.w, r.w, k, act, slope, po);
+    vo[i] = v;
+  }
+  for (int j = tid; j < s.nscalar; j += stride) {
+    const int e = scalar_index(s, j);
+    o[e] = apply_add_value(p[e], q[e], k, act, slope, po);
+  }
+}
+
+// g = grad_y * act'(y) from the forward's OUTPUT y (act_backward's edge rules hold for y as they do for z: sign(y) = sign(z + r) for
+// slope >= 0), written out, and accumulated exactly as bwd_value accumulates a grad_y that needs no mask
+__device__ __forceinline__ float bwd_add_value(float x, float gy, float y, float mean, float invstd, int act, float slope, Acc2& s) {
+  const float g = act_backward(y, gy, act, slope);
+  const float xh = (x - mean) * invstd;
+  s.a += (double)g;
+  s.b += (double)g * (double)xh;
+  return g;
+}
+
+// the grid, the loops, the tree and the combine launch of dd_bn_backward_reduce_kernel: on mutually aligned tensors sums2 has the bits
+// dd_bn_backward_reduce(x, g, act none) gives
+__global__ __launch_bounds__(kThreads) void dd_bn_backward_reduce_add_kernel(const float* __restrict__ x, const float* __restrict__ grad_y,
+                                                                             const float* __restrict__ y,
+                                                                             const float* __restrict__ mean_invstd, float* __restrict__ g,
+                                                                             double* __restrict__ partials, int act, float slope, int C,
+                                                                             int hw) {
+  __shared__ double lds[8];
+  const int c = blockIdx.y;
+  const float mean = mean_invstd[c], invstd = mean_invstd[C + c];
+  const size_t base = ((size_t)blockIdx.z * C + c) * (size_t)hw;
+  const float* p = x + base;
+  const float* q = grad_y + base;
+  const float* t = y + base;
+  float* o = g + base;
+  const Span s = make_span(p, q, t, o, hw);
+  const int tid = blockIdx.x * kThreads + threadIdx.x, stride = gridDim.x * kThreads;
+  const float4* vp = reinterpret_cast<const float4*>(p + s.head);
+  const float4* vq = reinterpret_cast<const float4*>(q + s.head);
+  const float4* vt = reinterpret_cast<const float4*>(t + s.head);
+  float4* vo = reinterpret_cast<float4*>(o + s.head);
+  Acc2 acc;
+  int i = tid;
+  for (; i + stride < s.nvec; i += 2 * stride) {      // two 16-byte loads per tensor in flight per thread
+    const float4 a0 = vp[i], a1 = vp[i + stride], g0 = vq[i], g1 = vq[i + stride], y0 = vt[i], y1 = vt[i + stride];
+    float4 r0, r1;
+    r0.x = bwd_add_value(a0.x, g0.x, y0.x, mean, invstd, act, slope, acc); r0.y = bwd_add_value(a0.y, g0.y, y0.y, mean, invstd, act, slope, acc);
+    r0.z = bwd_add_value(a0.z, g0.z, y0.z, mean, invstd, act, slope, acc); r0.w = bwd_add_value(a0.w, g0.w, y0.w, mean, invstd, act, slope, acc);
+    r1.x = bwd_add_value(a1.x, g1.x, y1.x, mean, invstd, act, slope, acc); r1.y = bwd_add_value(a1.y, g1.y, y1.y, mean, invstd, act, slope, acc);
+    r1.z = bwd_add_value(a1.z, g1.z, y1.z, mean, invstd, act, slope, acc); r1.w = bwd_add_value(a1.w, g1.w, y1.w, mean, invstd, act, slope, acc);
+    vo[i] = r0;
+    vo[i + stride] = r1;
+  }
+  for (; i < s.nvec; i += stride) {
+    const float4 a = vp[i], gq = vq[i], yy = vt[i];
+    float4 r;
+    r.x = bwd_add_value(a.x, gq.x, yy.x, mean, invstd, act, slope, acc); r.y = bwd_add_value(a.y, gq.y, yy.y, mean, invstd, act, slope, acc);
+    r.z = bwd_add_value(a.z, gq.z, yy.z, mean, invstd, act, slope, acc); r.w = bwd_add_value(a.w, gq.w, yy.w, mean, invstd, act, slope, acc);
+    vo[i] = r;
+  }
+  for (int j = tid; j < s.nscalar; j += stride) {
+    const int e = scalar_index(s, j);
+    o[e] = bwd_add_value(p[e], q[e], t[e], mean, invstd, act, slope, acc);
+  }
+  store_partial(partials, block_reduce2(acc.a, acc.b, lds));
+}
+
 double* partial_slab(void* workspace) { return reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + kHeaderBytes); }
 
 }  // namespace
@@ -344,6 +457,23 @@ hipError_t launch_backward_apply(const float* x, const float* grad_y, const floa
                                  hipStream_t st) {
   hipLaunchKernelGGL(dd_bn_backward_apply_kernel, dim3((unsigned)groups_for(hw), (unsigned)C, (unsigned)B), dim3(kThreads), 0, st, x, grad_y,
                      mean_invstd, weight, bias, sums2, sums, grad_x, act, slope, C, hw);
+  return hipGetLastError();
+}
+
+hipError_t launch_apply_add(const float* x, const float* mean_invstd, const float* weight, const float* bias, const float* addend, float* y,
+                            int act, float slope, int post, int B, int C, int hw, hipStream_t st) {
+  hipLaunchKernelGGL(dd_bn_apply_add_kernel, dim3((unsigned)groups_for(hw), (unsigned)C, (unsigned)B), dim3(kThreads), 0, st, x, mean_invstd,
+                     weight, bias, addend, y, act, slope, post, C, hw);
+  return hipGetLastError();
+}
+
+hipError_t launch_backward_reduce_add(const float* x, const float* grad_y, const float* y, const float* mean_invstd, int act, float slope,
+                                      float* g, double* sums2, void* workspace, int B, int C, int hw, hipStream_t st) {
+  const int G = groups_for(hw);
+  double* partials = partial_slab(workspace);
+  hipLaunchKernelGGL(dd_bn_backward_reduce_add_kernel, dim3((unsigned)G, (unsigned)C, (unsigned)B), dim3(kThreads), 0, st, x, grad_y, y,
+                     mean_invstd, g, partials, act, slope, C, hw);
+  hipLaunchKernelGGL(dd_bn_combine_kernel, dim3((unsigned)C), dim3(kThreads), 0, st, (const double*)partials, sums2, B * G, C, -1.0);
   return hipGetLastError();
 }
 

@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import modules as _modules
-from .batchnorm import convert_hip_batchnorm, resolve_bn_backend
+from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm, resolve_bn_backend
 from .codec import convert_hip_codec, resolve_codec_backend
 from .conv import convert_hip_conv, resolve_conv_backend, resolve_conv_grad_autoscale
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
@@ -74,7 +74,10 @@ class DDIMDepthEstimate_Res(nn.Module):
                            forward); "auto" = "cpu" in .train() -- the reference's training RNG stream -- and "device" in eval.
         bn_backend         "torch" [default] or "hip" (None = $DDEPTH_BN_BACKEND, else "torch"): with "hip" every BatchNorm2d of the FPN, the
                            codec and the neck becomes a batchnorm.HipBatchNorm2d holding the same tensors, its ReLU / LeakyReLU fused, so
-                           the .train() forward and backward of those layers run in csrc/dd_bn.hip (same state-dict keys; eval unchanged)
+                           the .train() forward and backward of those layers run in csrc/dd_bn.hip (same state-dict keys; eval unchanged).
+                           "hip+add" does the same and runs the FPN's top-down add inside the lateral BatchNorm's apply wherever conv_up's
+                           map already has the lateral map's size (every even pyramid: the pool is the identity there) and the tensors are
+                           native; any other site evaluates ``cur + adaptive_avg_pool2d(...)`` as before.  Same bits as "hip".
         conv_backend       "torch" [default] or "hip" (None = $DDEPTH_CONV_BACKEND, else "torch"): with "hip" the Conv3x3 of every conv_lateral and
                            the ConvTranspose2d of every conv_up become conv.HipConv2d / conv.HipConvTranspose2d holding the same tensors, so
                            their .train() forward and backward run in csrc/dd_conv.hip on `precision` operands ("bf16" / "f16" / "f16x3"; any
@@ -158,11 +161,15 @@ class DDIMDepthEstimate_Res(nn.Module):
         if self._hip_neck:
             bound.register("hahineck.", self.hahineck)
         self.bn_backend = resolve_bn_backend(bn_backend)
-        if self.bn_backend == "hip":
+        if self.bn_backend in ("hip", "hip+add"):
             # (convup_fp never runs; it is converted too so that every BatchNorm of the head is handled alike)
             for name in ("conv_lateral", "conv_up", "depth_transform", "hahineck", "convup_fp"):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_batchnorm(getattr(self, name)))
+        if self.bn_backend == "hip+add":
+            # the top-down add joins behind the lateral ReLU: aggregate_condition hands conv_up's map to these as their addend
+            for lateral in self.conv_lateral:
+                lateral[1].add_mode = "post"
         self.conv_backend = resolve_conv_backend(conv_backend)
         channels = "any" if self.conv_backend == "hip+all" else "block64"
         self.conv_grad_autoscale = resolve_conv_grad_autoscale(conv_grad_autoscale)
@@ -204,11 +211,30 @@ class DDIMDepthEstimate_Res(nn.Module):
         n = len(fp)
         for i in range(n):
             f = fp[n - i - 1]
-            cur = self.conv_lateral[n - i - 1](f)
-            if i > 0:
-                cur = cur + F.adaptive_avg_pool2d(self.conv_up[n - i - 1](x), output_size=cur.shape[-2:])
+            lateral = self.conv_lateral[n - i - 1]
+            if i > 0 and self.bn_backend == "hip+add":
+                cur = self._lateral_add(lateral, f, self.conv_up[n - i - 1](x))
+            else:
+                cur = lateral(f)
+                if i > 0:
+                    cur = cur + F.adaptive_avg_pool2d(self.conv_up[n - i - 1](x), output_size=cur.shape[-2:])
             x = cur
         return x
+
+    @staticmethod
+    def _lateral_add(lateral, f, top):
+        """lateral(f) + adaptive_avg_pool2d(top, lateral(f)'s size) with the add inside the lateral BatchNorm's apply ("post" mode) where the
+        pool is the identity (top already has the lateral map's size), the BatchNorm is a HipBatchNorm2d carrying the ReLU and both tensors
+        are native to the library; the expression itself anywhere else.  Same bits either way."""
+        bn = lateral[1] if len(lateral) == 3 else None
+        if isinstance(bn, HipBatchNorm2d) and bn.add_mode == "post" and type(lateral[2]) is nn.Identity:
+            z = lateral[0](f)
+            if top.shape == z.shape and bn._native(z) and bn._native_addend(z, top):
+                return bn(z, addend=top)
+            cur = lateral[2](bn(z))
+        else:
+            cur = lateral(f)
+        return cur + F.adaptive_avg_pool2d(top, output_size=cur.shape[-2:])
 
     def forward(self, fp, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kwargs):
         # parameters do not change inside one forward: verify / upload them once, not in front of each of its ~7 library calls

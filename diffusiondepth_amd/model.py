@@ -15,6 +15,7 @@ from types import SimpleNamespace
 import torch
 from torch import nn
 
+from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
 from .conv import convert_hip_conv
 from .head import build_head
 
@@ -29,9 +30,14 @@ class _BasicBlock(nn.Module):
         self.relu = nn.ReLU(inplace=True)
         # the reference passes a bare 3x3 conv (with bias) as the first block's downsample (mmbev_resnet.py:128-129)
         self.downsample = nn.Conv2d(cin, cout, 3, stride, 1) if first else None
+        # set by fuse_basic_block_tails: both BatchNorms are batchnorm.HipBatchNorm2d carrying their ReLU, and bn2 takes the residual as its addend
+        self.fused_tail = False
 
     def forward(self, x):
         idt = x if self.downsample is None else self.downsample(x)
+        if self.fused_tail:
+            out = self.bn1(self.conv1(x))
+            return self.bn2(self.conv2(out), addend=idt)
         out = self.relu(self.bn1(self.conv1(x)))
         out = self.bn2(self.conv2(out))
         return self.relu(out + idt)
@@ -93,12 +99,31 @@ def resolve_backbone(args):
     return getattr(module, name)
 
 
+def fuse_basic_block_tails(backbone: nn.Module) -> nn.Module:
+    """Every ``_BasicBlock`` of ``backbone`` whose bn1 and bn2 are ``HipBatchNorm2d`` (after ``convert_hip_batchnorm``) runs
+    ``bn1 = BatchNorm + ReLU`` and ``bn2 = ReLU(BatchNorm + identity)`` as one library call each (include/ddepth_bn_add.h): no torch add, no
+    torch ReLU.  Same parameter tensors and state-dict keys; ``relu`` stays an attribute.  Blocks on other BatchNorms are left alone;
+    calling it again changes nothing.  On CPU tensors, in .eval() and for other dtypes the BatchNorms take their torch path and the block
+    computes what it computed."""
+    for m in backbone.modules():
+        if isinstance(m, _BasicBlock) and isinstance(m.bn1, HipBatchNorm2d) and isinstance(m.bn2, HipBatchNorm2d):
+            m.bn1.activation = "relu"
+            m.bn2.activation = "relu"
+            m.bn2.add_mode = "pre"
+            m.fused_tail = True
+    return backbone
+
+
+BACKBONE_BACKENDS = ("torch", "hip", "hip+bn")
+
+
 def resolve_backbone_backend(backbone_backend=None) -> str:
-    """``args.backbone_backend`` / the environment variable DDEPTH_BACKBONE_BACKEND: "torch" (default; empty or absent) or "hip" (the backbone's
-    convolutions run in the library, the stride-2 openings of every stage included)."""
+    """``args.backbone_backend`` / the environment variable DDEPTH_BACKBONE_BACKEND: "torch" (default; empty or absent), "hip" (the backbone's
+    convolutions run in the library, the stride-2 openings of every stage included) or "hip+bn" ("hip", and at every precision the backbone's
+    BatchNorms run in the library with each BasicBlock's ReLUs and residual add fused: convert_hip_batchnorm + fuse_basic_block_tails)."""
     choice = backbone_backend or os.environ.get("DDEPTH_BACKBONE_BACKEND") or "torch"
-    if choice not in ("torch", "hip"):
-        raise ValueError(f"backbone_backend must be 'torch' or 'hip' (got {choice!r})")
+    if choice not in BACKBONE_BACKENDS:
+        raise ValueError(f"backbone_backend must be one of {list(BACKBONE_BACKENDS)} (got {choice!r})")
     return choice
 
 
@@ -120,15 +145,19 @@ class Diffusion_DCbase_Model(nn.Module):
                                               loss_cfgs=[], init_cfg=None, precision=getattr(self.args, "precision", None)))
         # Opt-in: the (resolved or injected) backbone's convolutions in the library -- 3x3 s1 through dd_convx_*, the 3x3 s2 openings of every
         # stage (conv1, the biased downsample, the RGB one included) through dd_conv3x3s2_*.  Same parameter tensors, same state-dict keys.  With
-        # a precision the library does not run (fp32, f16r, None) nothing is converted, as in the heads.  The backbone's BatchNorms have no
-        # switch here: ``model.depth_backbone = convert_hip_batchnorm(model.depth_backbone)`` (batchnorm.py) serves them.
+        # a precision the library does not run (fp32, f16r, None) nothing is converted, as in the heads.  "hip+bn" adds the backbone's BatchNorms
+        # (below); with "hip" they stay torch modules.
         self.backbone_backend = resolve_backbone_backend(getattr(self.args, "backbone_backend", None))
-        if self.backbone_backend == "hip":
+        if self.backbone_backend in ("hip", "hip+bn"):
             precision = getattr(self.args, "precision", None)
             if precision is None:      # (the head resolved its own: profile / DDEPTH_PRECISION)
                 precision = getattr(getattr(self.depth_head, "model", None), "precision", None)
             self.depth_backbone = convert_hip_conv(self.depth_backbone, precision, channels="any", strided=True,
                                                    grad_autoscale=bool(getattr(self.depth_head, "conv_grad_autoscale", False)))
+        if self.backbone_backend == "hip+bn":
+            # BatchNorm is fp32 whatever the convolutions' precision: every BatchNorm of the backbone in the library, and in the bundled BasicBlock
+            # stacks the two ReLUs and the residual add of each block inside those calls
+            self.depth_backbone = fuse_basic_block_tails(convert_hip_batchnorm(self.depth_backbone))
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125
