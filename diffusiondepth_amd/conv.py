@@ -32,6 +32,11 @@ The backbone (opt-in, ``strided``).  model.ResNetForMMBEV opens every stage with
 when asked to, and the default replaces exactly what it always replaced:
 
     convert_hip_conv(backbone, "bf16", channels="any", strided=True)       # or: args.backbone_backend="hip" / DDEPTH_BACKBONE_BACKEND=hip
+
+The backbone in .eval() (opt-in, include/ddepth_conv_fused.h).  There a BatchNorm is a per-channel scale and shift: ``conv_bn_act(conv, bn, x, addend, relu)``
+folds it on the device (``bn_fold``) and runs the 3x3 convolution, stride 1 or 2, with scale, shift, the residual add and the ReLU where the accumulator is
+stored (``conv_affine_forward``) -- no torch BatchNorm, add or ReLU.  It keeps nothing for a backward and returns None where the call is not native, so the
+caller falls back; model.fold_eval_basic_blocks / ``backbone_backend="hip+fold"`` use it for every BasicBlock under no_grad.
 """
 from __future__ import annotations
 
@@ -59,6 +64,9 @@ ABI_SYMBOLS_SCALED = ["dd_conv_grad_scale", "dd_convx_backward_data_scaled", "dd
 ABI_SYMBOLS_STRIDED = ["dd_conv3x3s2_supported", "dd_conv3x3s2_workspace_bytes", "dd_conv3x3s2_forward", "dd_conv3x3s2_backward_data",
                        "dd_conv3x3s2_backward_weight"]
 
+# every symbol include/ddepth_conv_fused.h declares (tests/test_conv_fused_cpu.py): the folded eval-mode forward; bound on first use as well
+ABI_SYMBOLS_FUSED = ["dd_bn_fold", "dd_conv3x3_affine_supported", "dd_conv3x3_affine_workspace_bytes", "dd_conv3x3_affine_forward"]
+
 OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
 _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
@@ -75,6 +83,7 @@ _ENTRY_SCALED = (None, "dd_convx_backward_data_scaled", "dd_convx_backward_weigh
 _bound = None
 _bound_scaled = None
 _bound_strided = None
+_bound_fused = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
 
@@ -127,6 +136,20 @@ def _lib_strided():
         lib.dd_conv3x3s2_backward_weight.restype, lib.dd_conv3x3s2_backward_weight.argtypes = c_int, [c_vp] * 6 + [c_int] * 6 + [c_vp]
         _bound_strided = lib
     return _bound_strided
+
+
+def _lib_fused():
+    global _bound_fused
+    if _bound_fused is None:
+        lib = _lib()
+        c_int, c_vp = ctypes.c_int, ctypes.c_void_p
+        lib.dd_bn_fold.restype, lib.dd_bn_fold.argtypes = c_int, [c_vp] * 4 + [ctypes.c_double] + [c_vp] * 2 + [c_int, c_vp]
+        lib.dd_conv3x3_affine_supported.restype, lib.dd_conv3x3_affine_supported.argtypes = c_int, [c_int] * 4
+        lib.dd_conv3x3_affine_workspace_bytes.restype = c_int
+        lib.dd_conv3x3_affine_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+        lib.dd_conv3x3_affine_forward.restype, lib.dd_conv3x3_affine_forward.argtypes = c_int, [c_vp] * 6 + [c_int] * 8 + [c_vp]
+        _bound_fused = lib
+    return _bound_fused
 
 
 def _ck(rc, what):
@@ -568,6 +591,111 @@ class HipConvTranspose2d(nn.ConvTranspose2d):
         if not self._native(x, output_size):
             return super().forward(x, output_size)
         return _apply(ConvTranspose2x2Function, x, self.weight, precision_id(self.precision), self.channels, self.grad_autoscale)
+
+
+# ---- the folded eval-mode forward (include/ddepth_conv_fused.h): convolution + BatchNorm + residual + ReLU in one kernel -------------------------------
+def supported_affine(stride: int, cin: int, cout: int, precision) -> bool:
+    """dd_conv3x3_affine_supported: stride 1 takes the range of dd_convx_supported(3x3), stride 2 that of dd_conv3x3s2_supported.  No device needed."""
+    p = precision_id(precision)
+    return p is not None and bool(_lib_fused().dd_conv3x3_affine_supported(int(stride), int(cin), int(cout), p))
+
+
+def _vector_native(t, n, device) -> bool:
+    return t is None or bool(t.is_cuda and t.device == device and t.dtype == torch.float32 and t.is_contiguous() and t.dim() == 1 and t.numel() == n)
+
+
+def _fold(bn, conv_bias, C: int, device) -> torch.Tensor:
+    vecs = [None] * 4 if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+    vecs = [v.detach() if v is not None else None for v in vecs + [conv_bias]]
+    for name, v in zip(("weight", "bias", "running_mean", "running_var", "conv_bias"), vecs):
+        if not _vector_native(v, C, torch.device(device)):
+            raise RuntimeError(f"{name} must be a contiguous fp32 vector of {C} elements on {device} (got {tuple(v.shape)} {v.dtype} on {v.device})")
+    if bn is not None and (vecs[2] is None or vecs[3] is None):
+        raise RuntimeError("the BatchNorm has no running statistics to fold")
+    scale_shift = torch.empty((2, C), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _ck(_lib_fused().dd_bn_fold(*[v.data_ptr() if v is not None else None for v in vecs[:4]], float(bn.eps) if bn is not None else 0.0,
+                                    vecs[4].data_ptr() if vecs[4] is not None else None, scale_shift.data_ptr(), C, _stream(scale_shift)),
+            "dd_bn_fold")
+    return scale_shift
+
+
+def bn_fold(bn, conv_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dd_bn_fold: the fp32 device tensor [2, C] = [scale | shift] of an eval-mode BatchNorm ``bn`` (``nn.BatchNorm2d`` or ``HipBatchNorm2d``; its
+    running statistics, eps and affine parameters) behind a convolution with the bias ``conv_bias``:
+    scale = weight / sqrt(running_var + eps), shift = bias + (conv_bias - running_mean) * scale, in fp64 on the device, rounded once.
+    ``bn=None``: the identity scale with ``conv_bias`` as the shift.  One tiny launch; nothing is cached, nothing synchronises the host."""
+    if bn is None:
+        if conv_bias is None:
+            raise ValueError("bn_fold needs a BatchNorm or a bias")
+        return _fold(None, conv_bias, int(conv_bias.numel()), conv_bias.device)
+    if bn.running_mean is None or bn.running_var is None:
+        raise RuntimeError("the BatchNorm has no running statistics to fold")
+    return _fold(bn, conv_bias, int(bn.num_features), bn.running_mean.device)
+
+
+def conv_affine_forward(x: torch.Tensor, w: torch.Tensor, scale_shift: torch.Tensor, addend: Optional[torch.Tensor], relu: bool, prec: int,
+                        stride: int = 1) -> torch.Tensor:
+    """relu(F.conv2d(x, w, None, stride, 1) * scale + shift + addend) through dd_conv3x3_affine_forward; ``scale_shift`` is [2, Cout] as ``bn_fold``
+    returns it, ``addend`` (the output's shape) may be None."""
+    _check_native(x, "x")
+    _check_native(w, "weight")
+    _check_native(scale_shift, "scale_shift")
+    if stride not in (1, 2):
+        raise ValueError(f"stride must be 1 or 2 (got {stride!r})")
+    dims = _s2_geometry(x, w)
+    B, _, cout, H, W = dims
+    if tuple(scale_shift.shape) != (2, cout) or scale_shift.device != x.device:
+        raise ValueError(f"scale_shift must be [2, {cout}] on {x.device} (got {tuple(scale_shift.shape)} on {scale_shift.device})")
+    shape = (B, cout, strided_out(H), strided_out(W)) if stride == 2 else (B, cout, H, W)
+    if addend is not None:
+        _check_native(addend, "addend")
+        if tuple(addend.shape) != shape or addend.device != x.device:
+            raise ValueError(f"addend must be {shape} on {x.device} (got {tuple(addend.shape)} on {addend.device})")
+    y = torch.empty(shape, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        need = ctypes.c_int64(0)
+        _ck(_lib_fused().dd_conv3x3_affine_workspace_bytes(int(stride), *dims, int(prec), ctypes.byref(need)), "dd_conv3x3_affine_workspace_bytes")
+        key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), int(need.value))
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = torch.empty(int(need.value), dtype=torch.uint8, device=x.device)
+            _workspaces[key] = ws
+        _ck(_lib_fused().dd_conv3x3_affine_forward(x.data_ptr(), w.data_ptr(), scale_shift.data_ptr(), addend.data_ptr() if addend is not None else None,
+                                                   y.data_ptr(), ws.data_ptr(), int(stride), int(bool(relu)), *dims, int(prec), _stream(x)),
+            "dd_conv3x3_affine_forward")
+    return y
+
+
+def conv_bn_act(conv, bn, x: torch.Tensor, addend: Optional[torch.Tensor] = None, relu: bool = True) -> Optional[torch.Tensor]:
+    """relu(bn(conv(x)) + addend) of an eval-mode block in two library launches behind the weight pack, or None where the call is not native
+    (the caller then takes its own path): ``conv`` must be a ``HipConv2d`` of the 3x3 pad-1 geometry, stride 1 (no bias) or 2 (a bias allowed),
+    of a precision and channel counts the operator runs; ``bn`` an ``nn.BatchNorm2d`` / ``HipBatchNorm2d`` with running statistics, or None
+    (identity scale, the conv's bias as the shift); every tensor a contiguous fp32 tensor on one HIP device.  Uses the RUNNING statistics and
+    keeps nothing for a backward: for .eval() under no_grad.  The fold runs on every call (one tiny launch), so it is never stale."""
+    if not isinstance(conv, HipConv2d):
+        return None
+    stride = 2 if _is_conv3x3s2(conv) else 1 if _is_conv3x3(conv) else None
+    if stride is None or not (_tensors_native(x, conv.weight) and x.shape[1] == conv.in_channels):
+        return None
+    cout, dev = conv.out_channels, x.device
+    if conv.weight.device != dev or not supported_affine(stride, conv.in_channels, cout, conv.precision):
+        return None
+    if not _vector_native(conv.bias, cout, dev):
+        return None
+    if bn is not None:
+        if (not isinstance(bn, nn.modules.batchnorm._BatchNorm) or bn.training or bn.num_features != cout or bn.running_mean is None
+                or bn.running_var is None):
+            return None
+        if not all(_vector_native(v, cout, dev) for v in (bn.weight, bn.bias, bn.running_mean, bn.running_var)):
+            return None
+    shape = (x.shape[0], cout) + ((strided_out(x.shape[2]), strided_out(x.shape[3])) if stride == 2 else tuple(x.shape[2:]))
+    if addend is not None and not (addend.is_cuda and addend.device == dev and addend.dtype == torch.float32 and addend.is_contiguous()
+                                   and tuple(addend.shape) == shape):
+        return None
+    scale_shift = _fold(bn, conv.bias, cout, dev)
+    return conv_affine_forward(x.detach(), conv.weight.detach(), scale_shift, addend.detach() if addend is not None else None, relu,
+                               precision_id(conv.precision), stride)
 
 
 def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64", strided: bool = False) -> bool:

@@ -1,9 +1,10 @@
-// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h, include/ddepth_conv_scaled.h and include/ddepth_conv_strided.h: argument checks and the
-// launch sequence; the kernels are in dd_conv.hip.
+// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h, include/ddepth_conv_scaled.h, include/ddepth_conv_strided.h and include/ddepth_conv_fused.h:
+// argument checks and the launch sequence; the kernels are in dd_conv.hip.
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_conv.h"
 #include "../../include/ddepth_conv_scaled.h"
 #include "../../include/ddepth_conv_strided.h"
+#include "../../include/ddepth_conv_fused.h"
 #include "dd_conv.h"
 #include "dd_status.h"
 
@@ -92,6 +93,13 @@ int check_s2(int B, int Cin, int Cout, int H, int W, int precision, int* prec) {
   if ((int64_t)H * (int64_t)W > (int64_t)INT_MAX / 4 || H > INT_MAX / 4 || W > INT_MAX / 4)
     return g_conv_err.fail(DD_ERR_INVALID_ARG, "H = %d, W = %d: 4 * H * W must fit an int", H, W);
   return DD_OK;
+}
+
+// include/ddepth_conv_fused.h: the checks of the stride's own operator
+int check_affine(int stride, int B, int Cin, int Cout, int H, int W, int precision, int* prec) {
+  if (stride == 1) return check(kChannelsExtended, DD_CONV_3X3, B, Cin, Cout, H, W, precision, prec);
+  if (stride == 2) return check_s2(B, Cin, Cout, H, W, precision, prec);
+  return g_conv_err.fail(DD_ERR_INVALID_ARG, "stride must be 1 or 2 (got %d)", stride);
 }
 
 }  // namespace
@@ -236,6 +244,47 @@ int dd_conv3x3s2_backward_weight(const float* x, const float* grad_y, float* gra
     return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
   DD_STATUS_HIP(g_conv_err,
                 ddconv::launch_conv_s2_wgrad(x, grad_y, grad_w, grad_bias, workspace, B, Cin, Cout, H, W, prec, (hipStream_t)stream, scale));
+  return DD_OK;
+}
+
+// ---- include/ddepth_conv_fused.h: the folded eval-mode forward, 3x3 pad 1, stride 1 or 2 ------------------------------------------------------------
+int dd_bn_fold(const float* weight, const float* bias, const float* running_mean, const float* running_var, double eps, const float* conv_bias,
+               float* scale_shift, int C, void* stream) {
+  if (!scale_shift) return g_conv_err.fail(DD_ERR_INVALID_ARG, "scale_shift is NULL");
+  if (C < 1) return g_conv_err.fail(DD_ERR_INVALID_ARG, "C must be positive (got %d)", C);
+  if ((running_mean == nullptr) != (running_var == nullptr))
+    return g_conv_err.fail(DD_ERR_INVALID_ARG, "running_mean and running_var must both be given, or both be NULL");
+  if (!(eps >= 0.0)) return g_conv_err.fail(DD_ERR_INVALID_ARG, "eps must not be negative (got %g)", eps);
+  for (const float* p : {weight, bias, running_mean, running_var, conv_bias})
+    if (p && p == scale_shift) return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_bn_fold(weight, bias, running_mean, running_var, eps, conv_bias, scale_shift, C, (hipStream_t)stream));
+  return DD_OK;
+}
+
+int dd_conv3x3_affine_supported(int stride, int Cin, int Cout, int precision) {
+  if (stride == 1) return supported(kChannelsExtended, DD_CONV_3X3, Cin, Cout, precision);
+  return stride == 2 ? dd_conv3x3s2_supported(Cin, Cout, precision) : 0;
+}
+
+int dd_conv3x3_affine_workspace_bytes(int stride, int B, int Cin, int Cout, int H, int W, int precision, int64_t* bytes) {
+  if (!bytes) return g_conv_err.fail(DD_ERR_INVALID_ARG, "bytes is NULL");
+  int prec = 0;
+  if (int rc = check_affine(stride, B, Cin, Cout, H, W, precision, &prec)) return rc;
+  *bytes = (int64_t)ddconv::workspace_bytes_affine(stride, Cin, Cout, prec);
+  return DD_OK;
+}
+
+int dd_conv3x3_affine_forward(const float* x, const float* w, const float* scale_shift, const float* addend, float* y, void* workspace, int stride,
+                              int relu, int B, int Cin, int Cout, int H, int W, int precision, void* stream) {
+  int prec = 0;
+  if (int rc = check_affine(stride, B, Cin, Cout, H, W, precision, &prec)) return rc;
+  if (int rc = ddstatus::check_ptrs(g_conv_err, x, w, y, workspace)) return rc;
+  if (!scale_shift) return g_conv_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  if ((const void*)scale_shift == (const void*)y || (addend && (const void*)addend == (const void*)y))
+    return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  if (relu != 0 && relu != 1) return g_conv_err.fail(DD_ERR_INVALID_ARG, "relu must be 0 or 1 (got %d)", relu);
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv_affine(stride, x, w, scale_shift, addend, y, workspace, relu, B, Cin, Cout, H, W, prec,
+                                                       (hipStream_t)stream));
   return DD_OK;
 }
 

@@ -75,4 +75,14 @@ hipError_t launch_conv_s2_dgrad(const float* grad_y, const float* w, float* grad
 hipError_t launch_conv_s2_wgrad(const float* x, const float* grad_y, float* grad_w, float* grad_bias, void* workspace, int B, int Cin, int Cout, int H,
                                 int W, int prec, hipStream_t st, const float* scale);
 
+// ---- the folded eval-mode forward of include/ddepth_conv_fused.h: 3x3 pad 1, stride 1 or 2, BatchNorm + residual + ReLU in the epilogue ------------------
+// scale_shift [2][Cout] (launch_bn_fold writes it: fp64 per channel, rounded once; mean and var both NULL: no normalisation); addend NULL or y's
+// layout; H, W = the INPUT size.  The workspace is the forward's packed weight image alone.  stride 1: the channel range of kChannelsExtended;
+// stride 2: channels_s2_in / channels_extended.
+size_t workspace_bytes_affine(int stride, int Cin, int Cout, int prec);
+hipError_t launch_bn_fold(const float* weight, const float* bias, const float* mean, const float* var, double eps, const float* conv_bias,
+                          float* scale_shift, int C, hipStream_t st);
+hipError_t launch_conv_affine(int stride, const float* x, const float* w, const float* scale_shift, const float* addend, float* y, void* workspace,
+                              int relu, int B, int Cin, int Cout, int H, int W, int prec, hipStream_t st);
+
 }  // namespace ddconv

@@ -27,6 +27,9 @@
 //                           from a third inclusion of the header that adds the bias to the epilogue (dd_conv_igemm_bias_kernel), the weight gradient is
 //                           dd_conv_wgrad <3, 2, 1>; the data gradient is dd_conv_s2_dgrad_kernel, which sorts the nine taps by the parity of the input pixel
 //                           (1 + 2 + 2 + 4 tap GEMMs per 2 x 2 pixels); dd_conv_bias_grad_kernel / _reduce_kernel sum grad_y per channel in fp64 in a fixed order.
+//   folded eval forward     include/ddepth_conv_fused.h (a BasicBlock in .eval()): dd_bn_fold_kernel turns a BatchNorm's running statistics and the conv's bias
+//                           into scale_shift[2][N]; dd_conv_igemm_affine_kernel, a fourth inclusion of the header, is the implicit GEMM <3, 1, 1> or <3, 2, 1> whose
+//                           epilogue stores relu(acc * scale + shift + addend).
 //   host side               gemm_kind(op, dir) is the one table of <KS, S, PAD, KC, SCATTER> and pack mode, gemm_shape adds N and K; the pack launch,
 //                           the GEMM launch, packed_halfs and workspace_bytes read them, so the three that must agree on the padded weight image to
 //                           the byte cannot drift apart.  dispatch() turns the runtime operand mode and channel contract into template arguments.
@@ -138,6 +141,7 @@ constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channe
 
 #define DD_CONV_SCALED 0
 #define DD_CONV_BIAS 0
+#define DD_CONV_AFFINE 0
 #include "dd_conv_kernels.h"
 #undef DD_CONV_SCALED
 #define DD_CONV_SCALED 1
@@ -149,6 +153,37 @@ constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channe
 #include "dd_conv_kernels.h"
 #undef DD_CONV_SCALED
 #undef DD_CONV_BIAS
+
+// the tail of dd_conv_igemm_affine_kernel's epilogue (include/ddepth_conv_fused.h): the residual, then a ReLU that keeps a NaN
+__device__ __forceinline__ float affine_tail(float v, const float* __restrict__ addend, size_t o, int relu) {
+  if (addend) v += addend[o];
+  if (relu) v = v < 0.0f ? 0.0f : v;      // (NaN < 0 is false)
+  return v;
+}
+
+#undef DD_CONV_AFFINE
+#define DD_CONV_SCALED 0
+#define DD_CONV_BIAS 0
+#define DD_CONV_AFFINE 1      // dd_conv_igemm_affine_kernel: the folded forward of include/ddepth_conv_fused.h
+#include "dd_conv_kernels.h"
+#undef DD_CONV_SCALED
+#undef DD_CONV_BIAS
+#undef DD_CONV_AFFINE
+
+// scale_shift[2][C] of an eval-mode BatchNorm behind a convolution with the bias conv_bias: one thread per channel, fp64, each result rounded once.
+//   scale = weight / sqrt(var + eps),  shift = bias + (conv_bias - mean) * scale;  weight, bias, conv_bias NULL: 1, 0, 0.
+// mean and var both NULL: no normalisation (scale = weight, shift = bias + conv_bias * weight) -- a bare biased convolution.
+__global__ __launch_bounds__(kThreads) void dd_bn_fold_kernel(const float* __restrict__ weight, const float* __restrict__ bias,
+                                                              const float* __restrict__ mean, const float* __restrict__ var, double eps,
+                                                              const float* __restrict__ conv_bias, float* __restrict__ scale_shift, int C) {
+  const int c = blockIdx.x * kThreads + threadIdx.x;
+  if (c >= C) return;
+  double s = weight ? (double)weight[c] : 1.0;
+  if (var) s /= sqrt((double)var[c] + eps);
+  const double m = mean ? (double)mean[c] : 0.0;
+  scale_shift[c] = (float)s;
+  scale_shift[C + c] = (float)((bias ? (double)bias[c] : 0.0) + ((conv_bias ? (double)conv_bias[c] : 0.0) - m) * s);
+}
 
 // ---- the scale of a gradient (include/ddepth_conv_scaled.h) -------------------------------------------------------------------------------------------
 // scale[2] = the bits of the largest FINITE |g[i]|, as an integer maximum of the bits of the non-negative floats (their order is that of the
@@ -418,6 +453,31 @@ hipError_t launch_s2_wgrad_prec(const float* x, const float* grad_y, float* grad
   return hipGetLastError();
 }
 
+// ---- the folded eval-mode forward (include/ddepth_conv_fused.h) ---------------------------------------------------------------------------------------
+// pack as the forward of the stride's operator packs, then the implicit GEMM of that row of the table with the affine epilogue
+template <int PREC, bool RAGGED>
+hipError_t launch_affine_prec(int stride, const float* x, const float* w, const float* scale_shift, const float* addend, float* y, void* workspace,
+                              int relu, int B, int Cin, int Cout, int H, int W, hipStream_t st) {
+  const GemmShape g = gemm_shape(stride == 2 ? kOpConv3S2 : kOpConv3, 0, Cin, Cout);
+  const int Ho = stride == 2 ? strided_out(H) : H, Wo = stride == 2 ? strided_out(W) : W;
+  uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
+  uint16_t* wl = wh + packed_halfs(g);
+  hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(packed_halfs(g))), dim3(kThreads), 0, st, w, wh, wl, g.pack_mode, g.N, g.K,
+                     g.taps, g.kstep);
+  const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
+  const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)((g.N + kTileN - 1) / kTileN), (unsigned)B);
+  if (stride == 2) {
+    constexpr GemmKind k = gemm_kind(kOpConv3S2, 0);
+    hipLaunchKernelGGL((dd_conv_igemm_affine_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>), grid, dim3(kThreads), 0, st, x,
+                       (const uint16_t*)wh, (const uint16_t*)wl, y, g.K, g.N, H, W, Ho, Wo, tiles_x, scale_shift, addend, relu);
+  } else {
+    constexpr GemmKind k = gemm_kind(kOpConv3, 0);
+    hipLaunchKernelGGL((dd_conv_igemm_affine_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>), grid, dim3(kThreads), 0, st, x,
+                       (const uint16_t*)wh, (const uint16_t*)wl, y, g.K, g.N, H, W, Ho, Wo, tiles_x, scale_shift, addend, relu);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
@@ -503,6 +563,26 @@ hipError_t launch_conv_s2_wgrad(const float* x, const float* grad_y, float* grad
   return dispatch(prec, Cin, Cout, scale != nullptr, [&](auto p, auto ragged, auto scaled) {
     return launch_s2_wgrad_prec<decltype(p)::value, decltype(ragged)::value, decltype(scaled)::value>(x, grad_y, grad_w, grad_bias, workspace, scale,
                                                                                                       B, Cin, Cout, H, W, st);
+  });
+}
+
+// ---- the folded eval-mode forward --------------------------------------------------------------------------------------------------------------------
+size_t workspace_bytes_affine(int stride, int Cin, int Cout, int prec) {
+  const size_t packed = packed_halfs(stride == 2 ? kOpConv3S2 : kOpConv3, 0, Cin, Cout) * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
+  return (packed + 255) / 256 * 256;
+}
+
+hipError_t launch_bn_fold(const float* weight, const float* bias, const float* mean, const float* var, double eps, const float* conv_bias,
+                          float* scale_shift, int C, hipStream_t st) {
+  hipLaunchKernelGGL(dd_bn_fold_kernel, dim3(blocks_for((size_t)C)), dim3(kThreads), 0, st, weight, bias, mean, var, eps, conv_bias, scale_shift, C);
+  return hipGetLastError();
+}
+
+hipError_t launch_conv_affine(int stride, const float* x, const float* w, const float* scale_shift, const float* addend, float* y, void* workspace,
+                              int relu, int B, int Cin, int Cout, int H, int W, int prec, hipStream_t st) {
+  return dispatch(prec, Cin, Cout, false, [&](auto p, auto ragged, auto) {
+    return launch_affine_prec<decltype(p)::value, decltype(ragged)::value>(stride, x, w, scale_shift, addend, y, workspace, relu, B, Cin, Cout, H, W,
+                                                                           st);
   });
 }
 

@@ -1,5 +1,6 @@
 // dd_conv_kernels.h -- the GEMM kernels of csrc/dd_conv.hip, written ONCE and included there TWICE (and a third time, DD_CONV_BIAS 1, for the biased
-// forward of include/ddepth_conv_strided.h alone: below): with DD_CONV_SCALED 0 it defines the kernels of include/ddepth_conv.h and ddepth_conv_strided.h
+// forward of include/ddepth_conv_strided.h alone, and a fourth, DD_CONV_AFFINE 1, for the folded eval-mode forward of include/ddepth_conv_fused.h
+// alone: below): with DD_CONV_SCALED 0 it defines the kernels of include/ddepth_conv.h and ddepth_conv_strided.h
 // (dd_conv_igemm_kernel, dd_conv_wgrad_kernel, dd_conv1x1_gemm_kernel, dd_conv1x1_wgrad_kernel, dd_conv_wgrad_reduce_kernel, dd_conv_s2_dgrad_kernel,
 // dd_conv_bias_grad_kernel, dd_conv_bias_grad_reduce_kernel), with
 // DD_CONV_SCALED 1 their twins *_scaled_kernel of include/ddepth_conv_scaled.h, which take the device pair scale = {s, 1 / s} as one more (last)
@@ -19,7 +20,7 @@
 #define DD_CONV_SCALE_PARAM , const float* __restrict__ scale      /* the address is the same for every lane: scalar loads */
 #define DD_CONV_GY(is_grad_y, v) ((is_grad_y) ? (v) * scale[0] : (v))
 #define DD_CONV_UNSCALED(v) ((v) * scale[1])
-#define DD_CONV_BIASED(v, n) (v)
+#define DD_CONV_EPILOGUE(v, n, o) (v)
 #elif DD_CONV_BIAS
 // a third pass (include/ddepth_conv_strided.h): dd_conv_igemm_bias_kernel alone, the implicit GEMM with one more (last) argument bias[N] or NULL,
 // added in fp32 where the accumulator is stored.  Its own kernel for the reason the twins are: the argument list of dd_conv_igemm_kernel stays.
@@ -27,13 +28,24 @@
 #define DD_CONV_SCALE_PARAM , const float* __restrict__ bias
 #define DD_CONV_GY(is_grad_y, v) (v)
 #define DD_CONV_UNSCALED(v) (v)
-#define DD_CONV_BIASED(v, n) (bias ? (v) + bias[n] : (v))
+#define DD_CONV_EPILOGUE(v, n, o) (bias ? (v) + bias[n] : (v))
+#elif DD_CONV_AFFINE
+// a fourth pass (include/ddepth_conv_fused.h): dd_conv_igemm_affine_kernel alone, the implicit GEMM with three more (last) arguments -- scale_shift[2][N]
+// (an eval-mode BatchNorm folded by dd_bn_fold_kernel: row 0 the scale, row 1 the shift), addend (out's layout, or NULL) and relu.  Where the
+// accumulator is stored, in fp32:  v = fmaf(acc, scale[n], shift[n]);  with an addend v += addend[o];  with relu v = v < 0 ? 0 : v -- a NaN is not
+// below zero and stays one, as in torch (fmaxf(v, 0) would give 0).  One rounding for the fma, one for the add: two at most.  The expression sits
+// behind the guards of the store, so a RAGGED instantiation reads scale_shift for rows n < N only and addend inside the Ht x Wt grid only.
+#define DD_CONV_KERNEL(name) name##_affine_kernel
+#define DD_CONV_SCALE_PARAM , const float* __restrict__ scale_shift, const float* __restrict__ addend, int relu
+#define DD_CONV_GY(is_grad_y, v) (v)
+#define DD_CONV_UNSCALED(v) (v)
+#define DD_CONV_EPILOGUE(v, n, o) affine_tail(fmaf((v), scale_shift[n], scale_shift[N + (n)]), addend, (o), relu)
 #else
 #define DD_CONV_KERNEL(name) name##_kernel
 #define DD_CONV_SCALE_PARAM
 #define DD_CONV_GY(is_grad_y, v) (v)
 #define DD_CONV_UNSCALED(v) (v)
-#define DD_CONV_BIASED(v, n) (v)
+#define DD_CONV_EPILOGUE(v, n, o) (v)
 #endif
 
 // ---- forward and data gradient --------------------------------------------------------------------------------------------------------------------
@@ -126,13 +138,15 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_igemm)(const 
         const size_t oy = 2 * (size_t)y + (t4 >> 1), ox = 2 * (size_t)x + (t4 & 1);
         out[(((size_t)b * cout + co) * (2 * (size_t)Ht) + oy) * (2 * (size_t)Wt) + ox] = acc[nb][r];
       } else {
-        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = DD_CONV_BIASED(DD_CONV_UNSCALED(acc[nb][r]), n);
+        // (the index is said twice: every pass but the affine one drops the macro's last argument, and is then the text it always was)
+        out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] =
+            DD_CONV_EPILOGUE(DD_CONV_UNSCALED(acc[nb][r]), n, (((size_t)b * N + n) * Ht + y) * (size_t)Wt + x);
       }
     }
   }
 }
 
-#if !DD_CONV_BIAS      // (the bias pass: the implicit GEMM alone)
+#if !DD_CONV_BIAS && !DD_CONV_AFFINE      // (the bias and the affine pass: the implicit GEMM alone)
 // ---- weight gradient --------------------------------------------------------------------------------------------------------------------------------
 // P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
 //   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
@@ -569,10 +583,10 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_bias_grad_red
   for (int k = 1; k < chunks; ++k) s += part[(size_t)co * chunks + k];
   grad_bias[co] = DD_CONV_UNSCALED((float)s);
 }
-#endif      // !DD_CONV_BIAS
+#endif      // !DD_CONV_BIAS && !DD_CONV_AFFINE
 
 #undef DD_CONV_KERNEL
 #undef DD_CONV_SCALE_PARAM
 #undef DD_CONV_GY
 #undef DD_CONV_UNSCALED
-#undef DD_CONV_BIASED
+#undef DD_CONV_EPILOGUE

@@ -5,7 +5,10 @@ stem-less BasicBlock ResNet equivalent of the reference's mmbev_res18/50/101
 (reference src/model/backbone/mmbev_resnet.py:101-194, which needs mmdet) is provided so the whole
 model can run offline with random-init weights.  Opt-in (``args.backbone_backend="hip"`` /
 DDEPTH_BACKBONE_BACKEND=hip): the backbone's convolutions run in the library (conv.convert_hip_conv
-with ``channels="any", strided=True``); the default leaves the backbone as it is.
+with ``channels="any", strided=True``); the default leaves the backbone as it is.  ``"hip+bn"`` adds the
+BatchNorms with the block tails fused for .train(), ``"hip+fold"`` also runs every BasicBlock in .eval() under
+no_grad as convolutions with BatchNorm, add and ReLU in their epilogues; ``args.backbone_precision`` /
+DDEPTH_BACKBONE_PRECISION gives the backbone a precision of its own.
 """
 from __future__ import annotations
 
@@ -16,7 +19,7 @@ import torch
 from torch import nn
 
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
-from .conv import convert_hip_conv
+from .conv import conv_bn_act, convert_hip_conv
 from .head import build_head
 
 
@@ -32,8 +35,25 @@ class _BasicBlock(nn.Module):
         self.downsample = nn.Conv2d(cin, cout, 3, stride, 1) if first else None
         # set by fuse_basic_block_tails: both BatchNorms are batchnorm.HipBatchNorm2d carrying their ReLU, and bn2 takes the residual as its addend
         self.fused_tail = False
+        # set by fold_eval_basic_blocks: in .eval() without grad the block is two or three library calls (conv.conv_bn_act), each a convolution with the
+        # folded BatchNorm, the residual add and the ReLU in its epilogue
+        self.folded_eval = False
+
+    def _forward_folded(self, x):
+        """The eval-mode block in the library, or None where one of its calls is not native (nothing has been changed then)."""
+        out = conv_bn_act(self.conv1, self.bn1, x, relu=True)
+        if out is None:
+            return None
+        idt = x if self.downsample is None else conv_bn_act(self.downsample, None, x, relu=False)
+        if idt is None:
+            return None
+        return conv_bn_act(self.conv2, self.bn2, out, addend=idt, relu=True)
 
     def forward(self, x):
+        if self.folded_eval and not self.training and not torch.is_grad_enabled():
+            out = self._forward_folded(x)
+            if out is not None:
+                return out
         idt = x if self.downsample is None else self.downsample(x)
         if self.fused_tail:
             out = self.bn1(self.conv1(x))
@@ -114,16 +134,41 @@ def fuse_basic_block_tails(backbone: nn.Module) -> nn.Module:
     return backbone
 
 
-BACKBONE_BACKENDS = ("torch", "hip", "hip+bn")
+def fold_eval_basic_blocks(backbone: nn.Module) -> nn.Module:
+    """Marks every ``_BasicBlock`` of ``backbone`` ``folded_eval``: in .eval() with grad disabled, on tensors and modules the library takes
+    (``HipConv2d`` convolutions after ``convert_hip_conv(..., channels="any", strided=True)``, BatchNorms with running statistics, contiguous fp32
+    HIP tensors), the block runs as two or three calls of include/ddepth_conv_fused.h -- no torch BatchNorm, add or ReLU.  Everywhere else
+    (.train(), grad enabled, CPU tensors, a convolution or precision the operator does not run) the block computes exactly what it computed.
+    Parameter tensors and state-dict keys are untouched; calling it again changes nothing."""
+    for m in backbone.modules():
+        if isinstance(m, _BasicBlock):
+            m.folded_eval = True
+    return backbone
+
+
+BACKBONE_BACKENDS = ("torch", "hip", "hip+bn", "hip+fold")
+BACKBONE_PRECISIONS = ("bf16", "f16", "f16x3")
 
 
 def resolve_backbone_backend(backbone_backend=None) -> str:
     """``args.backbone_backend`` / the environment variable DDEPTH_BACKBONE_BACKEND: "torch" (default; empty or absent), "hip" (the backbone's
-    convolutions run in the library, the stride-2 openings of every stage included) or "hip+bn" ("hip", and at every precision the backbone's
-    BatchNorms run in the library with each BasicBlock's ReLUs and residual add fused: convert_hip_batchnorm + fuse_basic_block_tails)."""
+    convolutions run in the library, the stride-2 openings of every stage included), "hip+bn" ("hip", and at every precision the backbone's
+    BatchNorms run in the library with each BasicBlock's ReLUs and residual add fused: convert_hip_batchnorm + fuse_basic_block_tails) or
+    "hip+fold" ("hip+bn", and in .eval() without grad every BasicBlock runs its convolutions with BatchNorm, residual add and ReLU folded into
+    their epilogues: fold_eval_basic_blocks -- one value for training and inference)."""
     choice = backbone_backend or os.environ.get("DDEPTH_BACKBONE_BACKEND") or "torch"
     if choice not in BACKBONE_BACKENDS:
         raise ValueError(f"backbone_backend must be one of {list(BACKBONE_BACKENDS)} (got {choice!r})")
+    return choice
+
+
+def resolve_backbone_precision(backbone_precision=None):
+    """``args.backbone_precision`` / the environment variable DDEPTH_BACKBONE_PRECISION: "bf16", "f16" or "f16x3" -- the operand precision of the
+    backbone's library convolutions, whatever the head's (a fast-profile "f16r" head can run an "f16x3" or "bf16" backbone) -- or None (empty or
+    absent: the backbone takes the head's precision, and is converted only where the library runs that one)."""
+    choice = backbone_precision or os.environ.get("DDEPTH_BACKBONE_PRECISION") or None
+    if choice is not None and choice not in BACKBONE_PRECISIONS:
+        raise ValueError(f"backbone_precision must be one of {list(BACKBONE_PRECISIONS)} (got {choice!r})")
     return choice
 
 
@@ -148,16 +193,23 @@ class Diffusion_DCbase_Model(nn.Module):
         # a precision the library does not run (fp32, f16r, None) nothing is converted, as in the heads.  "hip+bn" adds the backbone's BatchNorms
         # (below); with "hip" they stay torch modules.
         self.backbone_backend = resolve_backbone_backend(getattr(self.args, "backbone_backend", None))
-        if self.backbone_backend in ("hip", "hip+bn"):
-            precision = getattr(self.args, "precision", None)
+        # args.backbone_precision / DDEPTH_BACKBONE_PRECISION gives the backbone a precision of its own; absent, it takes the head's.
+        self.backbone_precision = resolve_backbone_precision(getattr(self.args, "backbone_precision", None))
+        if self.backbone_backend != "torch":
+            precision = self.backbone_precision
+            if precision is None:
+                precision = getattr(self.args, "precision", None)
             if precision is None:      # (the head resolved its own: profile / DDEPTH_PRECISION)
                 precision = getattr(getattr(self.depth_head, "model", None), "precision", None)
             self.depth_backbone = convert_hip_conv(self.depth_backbone, precision, channels="any", strided=True,
                                                    grad_autoscale=bool(getattr(self.depth_head, "conv_grad_autoscale", False)))
-        if self.backbone_backend == "hip+bn":
+        if self.backbone_backend in ("hip+bn", "hip+fold"):
             # BatchNorm is fp32 whatever the convolutions' precision: every BatchNorm of the backbone in the library, and in the bundled BasicBlock
             # stacks the two ReLUs and the residual add of each block inside those calls
             self.depth_backbone = fuse_basic_block_tails(convert_hip_batchnorm(self.depth_backbone))
+        if self.backbone_backend == "hip+fold":
+            # ... and in .eval() without grad each block's BatchNorms, add and ReLUs inside its convolutions' epilogues (include/ddepth_conv_fused.h)
+            self.depth_backbone = fold_eval_basic_blocks(self.depth_backbone)
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125
