@@ -22,11 +22,11 @@ from .head import (DDIMDepthEstimate_Res, DDIMDepthEstimate_Swin_ADD, DDIMDepthE
                    DDIMDepthEstimate_ResVis, DDIMDepthEstimate_Swin_ADDHAHIVis)
 from .necks import HAHIHeteroNeck
 from .nlspn import NLSPN
-from .model import Diffusion_DCbase_Model, fuse_basic_block_tails
+from .model import Diffusion_DCbase_Model, fuse_basic_block_tails, fuse_conv_bn_stats
 from .metric import Diffusion_DCbase_Metric, MetricAccumulator
 from .loss import Diffusion_DCbase_Loss
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
-from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv
+from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv, conv_bn_train
 from .codec import HipCodecConv2d, HipCodecConvTranspose2d, HipCodecTail, convert_hip_codec
 
 __all__ = [
@@ -36,6 +36,6 @@ __all__ = [
     "DDIMDepthEstimate_ResVis", "DDIMDepthEstimate_Swin_ADDHAHIVis", "HAHIHeteroNeck", "NLSPN", "Diffusion_DCbase_Model",
     "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
     "HipBatchNorm2d", "convert_hip_batchnorm", "fuse_basic_block_tails", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
-    "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec",
+    "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec", "fuse_conv_bn_stats", "conv_bn_train",
 ]
 __version__ = "0.1.0"

@@ -322,6 +322,83 @@ class BatchNormAddTrainFunction(Function):
         return (gx, gr if need_r else None, gw, gb) + none8
 
 
+def _check_sums(sums: torch.Tensor, x: torch.Tensor):
+    C = int(x.shape[1])
+    if not (sums.is_cuda and sums.device == x.device and sums.dtype == torch.float64 and sums.is_contiguous() and sums.numel() == 2 * C + 1):
+        raise RuntimeError(f"sums must be the contiguous fp64 vector of {2 * C + 1} elements bn_stats returns, on x's device "
+                           f"(got {tuple(sums.shape)} {sums.dtype} on {sums.device})")
+
+
+class BatchNormSumsTrainFunction(Function):
+    """BatchNormTrainFunction with the statistics ready: ``sums`` (last argument, not differentiable) is the (2C + 1) fp64 vector ``bn_stats(x)``
+    would compute -- conv.ConvStatsFunction writes it from the convolution's epilogue -- so dd_bn_stats does not run.  Everything behind it is
+    BatchNormTrainFunction's: the all-reduce of ``sums`` (in place) under ``exchange``, finalize and the running buffers, apply, the saved
+    tensors, and the backward itself."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, running_mean, running_var, eps, momentum, act, slope, exchange, sums):
+        _check_native(x, "x")
+        for name, p in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if p is not None:
+                _check_native(p, name)
+        sums = sums.detach()
+        _check_sums(sums, x)
+        w = weight.detach() if weight is not None else None
+        b = bias.detach() if bias is not None else None
+        if exchange is not None:
+            tdist.all_reduce(sums, group=exchange[0])
+        mean_invstd = bn_finalize(sums, eps, momentum, running_mean, running_var)
+        _touch(running_mean)
+        _touch(running_var)
+        y = bn_apply(x, mean_invstd, w, b, act, slope)
+        ctx.save_for_backward(x, mean_invstd, sums, weight, bias)
+        ctx.conf = (int(act), float(slope), exchange)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        return tuple(BatchNormTrainFunction.backward(ctx, grad_y)) + (None,)      # (the same saved tensors, the same first three inputs)
+
+
+class BatchNormAddSumsTrainFunction(Function):
+    """BatchNormAddTrainFunction with the statistics ready in ``sums`` (last argument), as BatchNormSumsTrainFunction: the statistics are those
+    of x alone in either ``add_mode``, so the convolution that wrote x can supply them."""
+
+    @staticmethod
+    def forward(ctx, x, addend, weight, bias, running_mean, running_var, eps, momentum, act, slope, add_mode, exchange, sums):
+        _check_native(x, "x")
+        _check_native(addend, "addend")
+        for name, p in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if p is not None:
+                _check_native(p, name)
+        if add_mode not in (ADD_PRE, ADD_POST):
+            raise ValueError(f"add_mode must be ADD_PRE or ADD_POST (got {add_mode!r})")
+        if add_mode == ADD_PRE and act == ACT_LEAKY_RELU and slope < 0:
+            raise RuntimeError("ADD_PRE with a LeakyReLU of negative slope: the output's sign is not the mask (HipBatchNorm2d takes the torch path)")
+        sums = sums.detach()
+        _check_sums(sums, x)
+        w = weight.detach() if weight is not None else None
+        b = bias.detach() if bias is not None else None
+        if exchange is not None:
+            tdist.all_reduce(sums, group=exchange[0])
+        mean_invstd = bn_finalize(sums, eps, momentum, running_mean, running_var)
+        _touch(running_mean)
+        _touch(running_var)
+        y = bn_apply_add(x, mean_invstd, addend.detach(), w, b, act, slope, add_mode)
+        if add_mode == ADD_PRE:
+            ctx.save_for_backward(x, y, mean_invstd, sums, weight)
+        else:
+            ctx.save_for_backward(x, mean_invstd, sums, weight, bias)
+        ctx.conf = (int(act), float(slope), int(add_mode), exchange)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        return tuple(BatchNormAddTrainFunction.backward(ctx, grad_y)) + (None,)      # (the same saved tensors, the same first four inputs)
+
+
 class HipBatchNorm2d(ddist.SyncBatchNorm):
     """``nn.BatchNorm2d`` (same parameters, buffers and state-dict keys) whose .train() forward and backward on a HIP device run in
     csrc/dd_bn.hip, with ``activation`` (None, "relu" or "leaky_relu" with ``negative_slope``) fused behind it.
@@ -387,6 +464,30 @@ class HipBatchNorm2d(ddist.SyncBatchNorm):
                                                    exchange)
         return BatchNormTrainFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
                                             ACTIVATIONS[self.activation], self.negative_slope, exchange)
+
+
+    def forward_sums(self, x, sums, addend=None):
+        """``forward(x, addend)`` on the library path with the statistics of x ready: ``sums`` is the (2C + 1) fp64 vector ``bn_stats(x)`` would
+        compute, written by whoever wrote x (conv.conv_bn_train: the convolution's epilogue), so no dd_bn_stats runs.  The caller has checked
+        what ``forward`` checks before it takes the library path (``_native``, ``_native_addend``); a tensor that is not native is an error
+        here, never a silent torch path, because ``sums`` would be dropped."""
+        self._check_input_dim(x)
+        if addend is not None and self.add_mode not in ADD_MODES:
+            raise ValueError(f"add_mode must be one of {list(ADD_MODES)} (got {self.add_mode!r})")
+        if not self._native(x) or (addend is not None and not self._native_addend(x, addend)):
+            raise RuntimeError("forward_sums needs what the library path needs: .train(), tracked running statistics, a fixed momentum and "
+                               "contiguous fp32 HIP tensors (an addend of x's shape)")
+        exchange = (self.process_group,) if self._exchanges() else None
+        if exchange is None and x.numel() // x.shape[1] == 1:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {x.size()}")
+        if self.num_batches_tracked is not None:
+            self.num_batches_tracked.add_(1)
+        if addend is not None:
+            return BatchNormAddSumsTrainFunction.apply(x, addend, self.weight, self.bias, self.running_mean, self.running_var, self.eps,
+                                                       self.momentum, ACTIVATIONS[self.activation], self.negative_slope,
+                                                       ADD_MODES[self.add_mode], exchange, sums)
+        return BatchNormSumsTrainFunction.apply(x, self.weight, self.bias, self.running_mean, self.running_var, self.eps, self.momentum,
+                                                ACTIVATIONS[self.activation], self.negative_slope, exchange, sums)
 
 
 def _from_batchnorm(m: nn.modules.batchnorm._BatchNorm, process_group) -> HipBatchNorm2d:

@@ -37,6 +37,12 @@ The backbone in .eval() (opt-in, include/ddepth_conv_fused.h).  There a BatchNor
 folds it on the device (``bn_fold``) and runs the 3x3 convolution, stride 1 or 2, with scale, shift, the residual add and the ReLU where the accumulator is
 stored (``conv_affine_forward``) -- no torch BatchNorm, add or ReLU.  It keeps nothing for a backward and returns None where the call is not native, so the
 caller falls back; model.fold_eval_basic_blocks / ``backbone_backend="hip+fold"`` use it for every BasicBlock under no_grad.
+
+A training conv -> BatchNorm pair (opt-in, include/ddepth_conv_stats.h).  In .train() a BatchNorm starts with a pass over the tensor its convolution
+has just written; ``conv_bn_train(conv, bn, x, addend)`` runs the 3x3 convolution, stride 1 or 2, with the per-channel fp64 sums taken in its epilogue
+(``conv_stats_forward`` / ``ConvStatsFunction``) and hands them to ``HipBatchNorm2d.forward_sums``: no dd_bn_stats.  The backward is the un-fused pair's.
+It returns None where one half is not native; model.fuse_conv_bn_stats / ``backbone_backend="hip+stats"`` and the heads' ``conv_bn_stats=True`` use it.
+Not covered: the transpose, pointwise and codec convolutions, and statistics in the backward.
 """
 from __future__ import annotations
 
@@ -67,6 +73,10 @@ ABI_SYMBOLS_STRIDED = ["dd_conv3x3s2_supported", "dd_conv3x3s2_workspace_bytes",
 # every symbol include/ddepth_conv_fused.h declares (tests/test_conv_fused_cpu.py): the folded eval-mode forward; bound on first use as well
 ABI_SYMBOLS_FUSED = ["dd_bn_fold", "dd_conv3x3_affine_supported", "dd_conv3x3_affine_workspace_bytes", "dd_conv3x3_affine_forward"]
 
+# every symbol include/ddepth_conv_stats.h declares (tests/test_conv_stats_cpu.py): the training forward that emits the BatchNorm statistics; bound on
+# first use as well
+ABI_SYMBOLS_STATS = ["dd_conv3x3_stats_supported", "dd_conv3x3_stats_workspace_bytes", "dd_conv3x3_stats_forward"]
+
 OP_CONV3X3, OP_DECONV2X2, OP_CONV1X1 = 0, 1, 2      # dd_conv_op
 LIBRARY_PRECISIONS = ("bf16", "f16", "f16x3")
 _LIBRARY_PRECISION_IDS = tuple(backend.PRECISIONS[p] for p in LIBRARY_PRECISIONS)
@@ -84,6 +94,7 @@ _bound = None
 _bound_scaled = None
 _bound_strided = None
 _bound_fused = None
+_bound_stats = None
 _workspaces: Dict[Tuple[int, int], torch.Tensor] = {}
 
 
@@ -150,6 +161,19 @@ def _lib_fused():
         lib.dd_conv3x3_affine_forward.restype, lib.dd_conv3x3_affine_forward.argtypes = c_int, [c_vp] * 6 + [c_int] * 8 + [c_vp]
         _bound_fused = lib
     return _bound_fused
+
+
+def _lib_stats():
+    global _bound_stats
+    if _bound_stats is None:
+        lib = _lib()
+        c_int, c_vp = ctypes.c_int, ctypes.c_void_p
+        lib.dd_conv3x3_stats_supported.restype, lib.dd_conv3x3_stats_supported.argtypes = c_int, [c_int] * 4
+        lib.dd_conv3x3_stats_workspace_bytes.restype = c_int
+        lib.dd_conv3x3_stats_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+        lib.dd_conv3x3_stats_forward.restype, lib.dd_conv3x3_stats_forward.argtypes = c_int, [c_vp] * 6 + [c_int] * 7 + [c_vp]
+        _bound_stats = lib
+    return _bound_stats
 
 
 def _ck(rc, what):
@@ -698,6 +722,102 @@ def conv_bn_act(conv, bn, x: torch.Tensor, addend: Optional[torch.Tensor] = None
                                precision_id(conv.precision), stride)
 
 
+# ---- the statistics-emitting training forward (include/ddepth_conv_stats.h): the convolution writes the BatchNorm's sums from its epilogue ------------
+def supported_stats(stride: int, cin: int, cout: int, precision) -> bool:
+    """dd_conv3x3_stats_supported: the ranges of ``supported_affine``.  No device needed."""
+    p = precision_id(precision)
+    return p is not None and bool(_lib_stats().dd_conv3x3_stats_supported(int(stride), int(cin), int(cout), p))
+
+
+def conv_stats_forward(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], stride: int, prec: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(y, sums) through dd_conv3x3_stats_forward: y = F.conv2d(x, w, bias, stride, 1), the bits ``conv_forward(OP_CONV3X3, ..., "any")`` /
+    ``conv_s2_forward`` give, and sums = the (2 Cout + 1) fp64 vector [sum y | sum y^2 | n] that ``batchnorm.bn_stats(y)`` would compute with a
+    pass over y (equal bit for bit where the sums are exact in fp64; elsewhere within the rounding of an fp64 sum)."""
+    _check_native(x, "x")
+    _check_native(w, "weight")
+    if stride not in (1, 2):
+        raise ValueError(f"stride must be 1 or 2 (got {stride!r})")
+    dims = _s2_geometry(x, w)
+    B, _, cout, H, W = dims
+    _check_vector(bias, "bias", cout, x)
+    y = torch.empty((B, cout, strided_out(H), strided_out(W)) if stride == 2 else (B, cout, H, W), dtype=torch.float32, device=x.device)
+    sums = torch.empty(2 * cout + 1, dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        need = ctypes.c_int64(0)
+        _ck(_lib_stats().dd_conv3x3_stats_workspace_bytes(int(stride), *dims, int(prec), ctypes.byref(need)), "dd_conv3x3_stats_workspace_bytes")
+        key = (x.device.index if x.device.index is not None else torch.cuda.current_device(), int(need.value))
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = torch.empty(int(need.value), dtype=torch.uint8, device=x.device)
+            _workspaces[key] = ws
+        _ck(_lib_stats().dd_conv3x3_stats_forward(x.data_ptr(), w.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
+                                                  sums.data_ptr(), ws.data_ptr(), int(stride), *dims, int(prec), _stream(x)),
+            "dd_conv3x3_stats_forward")
+    return y, sums
+
+
+class ConvStatsFunction(Function):
+    """(x, weight, bias or None, dd_precision, stride, channels, grad_autoscale) -> (y, sums) of ``conv_stats_forward``; ``sums`` is not
+    differentiable.  A bias is taken at stride 2 only (ValueError at stride 1).  The backward is the un-fused operator's: at stride 1 the calls of Conv3x3Function under the module's channel contract, at
+    stride 2 those of Conv3x3S2Function (the bias gradient from the weight gradient's call), ``grad_autoscale`` as there.  Kept: x and weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, prec, stride, channels="any", grad_autoscale=False):
+        if int(stride) == 1 and bias is not None:
+            # (the C ABI adds a bias at either stride, but the stride-1 backward is Conv3x3Function's, which has no bias gradient to give)
+            raise ValueError("ConvStatsFunction takes a bias at stride 2 only: the stride-1 operator of HipConv2d has none, and its backward "
+                             "computes no bias gradient (conv_stats_forward runs the biased stride-1 forward)")
+        ctx.save_for_backward(x, weight)
+        ctx.stride = int(stride)
+        ctx.prec = int(prec)                                  # (what Conv3x3S2Function.backward reads ...
+        ctx.conf = (OP_CONV3X3, int(prec), channels)          # ... and what _backward reads)
+        ctx.grad_autoscale = bool(grad_autoscale)
+        y, sums = conv_stats_forward(x, weight.detach(), bias.detach() if bias is not None else None, int(stride), int(prec))
+        ctx.mark_non_differentiable(sums)
+        return y, sums
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y, _grad_sums):
+        if ctx.stride == 2:
+            return tuple(Conv3x3S2Function.backward(ctx, grad_y)) + (None, None)      # (gx, gw, gb, None, None)
+        gx, gw = _backward(ctx, grad_y)[:2]
+        return gx, gw, None, None, None, None, None
+
+
+def conv_bn_train(conv, bn, x: torch.Tensor, addend: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:
+    """``bn(conv(x), addend)`` of a training conv -> BatchNorm pair with the BatchNorm's statistics taken from the convolution's epilogue (no
+    dd_bn_stats pass over conv's output), or None -- with nothing touched -- where one half is not native, so that the caller runs what it ran:
+    ``conv`` a ``HipConv2d`` that would run its 3x3 operator on x (stride 1, or ``strided`` stride 2 with or without a bias) at a shape and
+    precision dd_conv3x3_stats_supported takes; ``bn`` a ``batchnorm.HipBatchNorm2d`` in .train() that would run its library path (tracked
+    running statistics, a fixed momentum, fp32 parameters); ``addend`` None or a contiguous fp32 tensor of the output's shape on x's device that
+    the BatchNorm's ``add_mode`` takes; more than one value per channel unless the statistics are exchanged.  Everything behind the statistics
+    -- the SyncBN all-reduce of ``sums``, finalize and the running buffers, apply, the saved tensors, both backwards -- is what the un-fused pair
+    runs."""
+    from .batchnorm import HipBatchNorm2d
+    if not (isinstance(conv, HipConv2d) and isinstance(bn, HipBatchNorm2d) and bn.training and bn.num_features == conv.out_channels):
+        return None
+    if conv.strided and conv._native_s2(x):
+        stride = 2
+    elif conv._native(x) == OP_CONV3X3:
+        stride = 1
+    else:
+        return None
+    # bn._native is asked about x, the convolution's INPUT: of a tensor it reads only device kind, dtype and contiguity, and the BatchNorm's own input
+    # y is a fresh contiguous fp32 tensor that conv_stats_forward allocates on x's device, so the answer is y's.  (forward_sums asks again on y itself
+    # and raises where it does not hold: a mismatch cannot pass silently.)
+    if not (supported_stats(stride, conv.in_channels, conv.out_channels, conv.precision) and bn._native(x)):
+        return None
+    shape = (x.shape[0], conv.out_channels) + ((strided_out(x.shape[2]), strided_out(x.shape[3])) if stride == 2 else tuple(x.shape[2:]))
+    if addend is not None and not (tuple(addend.shape) == shape and bn.add_mode in ("pre", "post") and addend.device == x.device
+                                   and bn._native_addend(addend, addend)):      # (the output has the addend's shape: checked above)
+        return None
+    if shape[0] * shape[2] * shape[3] == 1 and not bn._exchanges():
+        return None
+    y, sums = ConvStatsFunction.apply(x, conv.weight, conv.bias, precision_id(conv.precision), stride, conv.channels, conv.grad_autoscale)
+    return bn.forward_sums(y, sums, addend)
+
+
 def eligible(m: nn.Module, precision, pointwise: bool = False, channels="block64", strided: bool = False) -> bool:
     """3x3 s1 p1 or transpose k2 s2 (with ``pointwise``: or 1x1 s1 p0), no bias, groups 1, dilation 1, and channel counts and a precision
     dd_conv_supported (``channels="any"``: dd_convx_supported) accepts.  With ``strided``: also 3x3 s2 p1, with or without a bias, that
@@ -769,4 +889,15 @@ def resolve_conv_grad_autoscale(conv_grad_autoscale: Optional[bool] = None) -> b
     choice = os.environ.get("DDEPTH_CONV_GRAD_AUTOSCALE") or "0"
     if choice not in ("0", "1"):
         raise ValueError(f"DDEPTH_CONV_GRAD_AUTOSCALE must be '0' or '1' (got {choice!r})")
+    return choice == "1"
+
+
+def resolve_conv_bn_stats(conv_bn_stats: Optional[bool] = None) -> bool:
+    """The head keyword ``conv_bn_stats`` / the environment variable DDEPTH_CONV_BN_STATS ("1" is on; "0", empty or absent is off, the default):
+    whether a converted conv_lateral in front of a ``HipBatchNorm2d`` emits that BatchNorm's statistics from its epilogue (``conv_bn_train``)."""
+    if conv_bn_stats is not None:
+        return bool(conv_bn_stats)
+    choice = os.environ.get("DDEPTH_CONV_BN_STATS") or "0"
+    if choice not in ("0", "1"):
+        raise ValueError(f"DDEPTH_CONV_BN_STATS must be '0' or '1' (got {choice!r})")
     return choice == "1"

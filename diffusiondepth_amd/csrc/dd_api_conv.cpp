@@ -1,10 +1,12 @@
-// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h, include/ddepth_conv_scaled.h, include/ddepth_conv_strided.h and include/ddepth_conv_fused.h:
+// dd_api_conv.cpp -- the C ABI of include/ddepth_conv.h, include/ddepth_conv_scaled.h, include/ddepth_conv_strided.h, include/ddepth_conv_fused.h and
+// include/ddepth_conv_stats.h:
 // argument checks and the launch sequence; the kernels are in dd_conv.hip.
 #include "../../include/ddepth.h"
 #include "../../include/ddepth_conv.h"
 #include "../../include/ddepth_conv_scaled.h"
 #include "../../include/ddepth_conv_strided.h"
 #include "../../include/ddepth_conv_fused.h"
+#include "../../include/ddepth_conv_stats.h"
 #include "dd_conv.h"
 #include "dd_status.h"
 
@@ -285,6 +287,30 @@ int dd_conv3x3_affine_forward(const float* x, const float* w, const float* scale
   if (relu != 0 && relu != 1) return g_conv_err.fail(DD_ERR_INVALID_ARG, "relu must be 0 or 1 (got %d)", relu);
   DD_STATUS_HIP(g_conv_err, ddconv::launch_conv_affine(stride, x, w, scale_shift, addend, y, workspace, relu, B, Cin, Cout, H, W, prec,
                                                        (hipStream_t)stream));
+  return DD_OK;
+}
+
+// ---- include/ddepth_conv_stats.h: the training forward that emits the BatchNorm statistics, 3x3 pad 1, stride 1 or 2 --------------------------------
+int dd_conv3x3_stats_supported(int stride, int Cin, int Cout, int precision) { return dd_conv3x3_affine_supported(stride, Cin, Cout, precision); }
+
+int dd_conv3x3_stats_workspace_bytes(int stride, int B, int Cin, int Cout, int H, int W, int precision, int64_t* bytes) {
+  if (!bytes) return g_conv_err.fail(DD_ERR_INVALID_ARG, "bytes is NULL");
+  int prec = 0;
+  if (int rc = check_affine(stride, B, Cin, Cout, H, W, precision, &prec)) return rc;
+  *bytes = (int64_t)ddconv::workspace_bytes_stats(stride, B, Cin, Cout, H, W, prec);
+  return DD_OK;
+}
+
+int dd_conv3x3_stats_forward(const float* x, const float* w, const float* bias, float* y, double* sums, void* workspace, int stride, int B, int Cin,
+                             int Cout, int H, int W, int precision, void* stream) {
+  int prec = 0;
+  if (int rc = check_affine(stride, B, Cin, Cout, H, W, precision, &prec)) return rc;
+  if (int rc = ddstatus::check_ptrs(g_conv_err, x, w, y, workspace)) return rc;
+  if (!sums) return g_conv_err.fail(DD_ERR_INVALID_ARG, "null pointer");
+  for (const void* p : {(const void*)x, (const void*)w, (const void*)bias})
+    if (p && (p == (const void*)y || p == (const void*)sums)) return g_conv_err.fail(DD_ERR_INVALID_ARG, "the output may not alias an input");
+  if ((const void*)sums == (const void*)y) return g_conv_err.fail(DD_ERR_INVALID_ARG, "the outputs may not alias each other");
+  DD_STATUS_HIP(g_conv_err, ddconv::launch_conv_stats(stride, x, w, bias, y, sums, workspace, B, Cin, Cout, H, W, prec, (hipStream_t)stream));
   return DD_OK;
 }
 

@@ -85,4 +85,12 @@ hipError_t launch_bn_fold(const float* weight, const float* bias, const float* m
 hipError_t launch_conv_affine(int stride, const float* x, const float* w, const float* scale_shift, const float* addend, float* y, void* workspace,
                               int relu, int B, int Cin, int Cout, int H, int W, int prec, hipStream_t st);
 
+// ---- the statistics-emitting forward of include/ddepth_conv_stats.h: 3x3 pad 1, stride 1 or 2, optional bias ---------------------------------------
+// y as launch_conv(kOpConv3, 0) / launch_conv_s2_forward store it; sums[2 Cout + 1] = [sum | sum of squares | B Ho Wo] of y per channel in fp64, the
+// layout of dd_bn_stats.  The workspace: the forward's packed weight image, then (256-byte aligned) the partials [Cout][B][tiles][2] fp64.
+// H, W = the INPUT size.  Channel ranges as workspace_bytes_affine.
+size_t workspace_bytes_stats(int stride, int B, int Cin, int Cout, int H, int W, int prec);
+hipError_t launch_conv_stats(int stride, const float* x, const float* w, const float* bias, float* y, double* sums, void* workspace, int B, int Cin,
+                             int Cout, int H, int W, int prec, hipStream_t st);
+
 }  // namespace ddconv

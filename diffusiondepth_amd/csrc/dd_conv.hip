@@ -30,6 +30,9 @@
 //   folded eval forward     include/ddepth_conv_fused.h (a BasicBlock in .eval()): dd_bn_fold_kernel turns a BatchNorm's running statistics and the conv's bias
 //                           into scale_shift[2][N]; dd_conv_igemm_affine_kernel, a fourth inclusion of the header, is the implicit GEMM <3, 1, 1> or <3, 2, 1> whose
 //                           epilogue stores relu(acc * scale + shift + addend).
+//   statistics forward      include/ddepth_conv_stats.h (a training conv in front of a BatchNorm): dd_conv_igemm_stats_kernel, a fifth inclusion of the header, is the
+//                           biased implicit GEMM <3, 1, 1> or <3, 2, 1> whose epilogue also sums the stored tile per channel in fp64 through the dead patch LDS;
+//                           dd_conv_stats_combine_kernel adds the per-tile pairs in a fixed order into the sums vector of dd_bn_stats.
 //   host side               gemm_kind(op, dir) is the one table of <KS, S, PAD, KC, SCATTER> and pack mode, gemm_shape adds N and K; the pack launch,
 //                           the GEMM launch, packed_halfs and workspace_bytes read them, so the three that must agree on the padded weight image to
 //                           the byte cannot drift apart.  dispatch() turns the runtime operand mode and channel contract into template arguments.
@@ -142,6 +145,7 @@ constexpr int wgrad_channel_stride(int halfs) {      // halfs between two channe
 #define DD_CONV_SCALED 0
 #define DD_CONV_BIAS 0
 #define DD_CONV_AFFINE 0
+#define DD_CONV_STATS 0
 #include "dd_conv_kernels.h"
 #undef DD_CONV_SCALED
 #define DD_CONV_SCALED 1
@@ -169,6 +173,43 @@ __device__ __forceinline__ float affine_tail(float v, const float* __restrict__ 
 #undef DD_CONV_SCALED
 #undef DD_CONV_BIAS
 #undef DD_CONV_AFFINE
+#undef DD_CONV_STATS
+#define DD_CONV_SCALED 0
+#define DD_CONV_BIAS 0
+#define DD_CONV_AFFINE 0
+#define DD_CONV_STATS 1      // dd_conv_igemm_stats_kernel: the statistics-emitting forward of include/ddepth_conv_stats.h
+#include "dd_conv_kernels.h"
+#undef DD_CONV_SCALED
+#undef DD_CONV_BIAS
+#undef DD_CONV_AFFINE
+#undef DD_CONV_STATS
+
+// sums[2 C + 1] = [sum | sum of squares | count] of a BatchNorm (the layout of dd_bn_stats) from the slab part[C][rows][2] that
+// dd_conv_igemm_stats_kernel wrote, rows = B * tiles: one workgroup per channel, thread t adds the rows t, t + 256, ... in that order, then a tree
+// over the 256 pairs in LDS.  The order depends on the shape alone: no atomics, the same bits on every run.
+__global__ __launch_bounds__(kThreads) void dd_conv_stats_combine_kernel(const double* __restrict__ part, double* __restrict__ sums, int rows, int C,
+                                                                         double count) {
+  __shared__ double lds[2][kThreads];
+  const int c = blockIdx.x, tid = threadIdx.x;
+  const double* row = part + (size_t)c * rows * 2;
+  double sa = 0.0, sb = 0.0;
+  for (int r = tid; r < rows; r += kThreads) {
+    sa += row[2 * r];
+    sb += row[2 * r + 1];
+  }
+  lds[0][tid] = sa;
+  lds[1][tid] = sb;
+  __syncthreads();
+  for (int d = kThreads / 2; d >= 1; d >>= 1) {
+    if (tid < d) {
+      lds[0][tid] += lds[0][tid + d];
+      lds[1][tid] += lds[1][tid + d];
+    }
+    __syncthreads();
+  }
+  if (tid < 2) sums[tid * C + c] = lds[tid][0];
+  if (c == 0 && tid == 0) sums[2 * C] = count;
+}
 
 // scale_shift[2][C] of an eval-mode BatchNorm behind a convolution with the bias conv_bias: one thread per channel, fp64, each result rounded once.
 //   scale = weight / sqrt(var + eps),  shift = bias + (conv_bias - mean) * scale;  weight, bias, conv_bias NULL: 1, 0, 0.
@@ -478,6 +519,40 @@ hipError_t launch_affine_prec(int stride, const float* x, const float* w, const 
   return hipGetLastError();
 }
 
+// ---- the statistics-emitting forward (include/ddepth_conv_stats.h) ------------------------------------------------------------------------------------
+// the weight image (twice in the split mode), rounded up to 256 bytes: where the partials start
+size_t stats_packed_bytes(int stride, int Cin, int Cout, int prec) {
+  const size_t packed = packed_halfs(gemm_shape(stride == 2 ? kOpConv3S2 : kOpConv3, 0, Cin, Cout)) * sizeof(uint16_t) * (prec == kPrecF16x3 ? 2 : 1);
+  return (packed + 255) / 256 * 256;
+}
+
+// pack as the forward of the stride's operator packs, the implicit GEMM of that row of the table with the statistics epilogue, then the combine
+template <int PREC, bool RAGGED>
+hipError_t launch_stats_prec(int stride, const float* x, const float* w, const float* bias, float* y, double* sums, void* workspace, int B, int Cin,
+                             int Cout, int H, int W, hipStream_t st) {
+  const GemmShape g = gemm_shape(stride == 2 ? kOpConv3S2 : kOpConv3, 0, Cin, Cout);
+  const int Ho = stride == 2 ? strided_out(H) : H, Wo = stride == 2 ? strided_out(W) : W;
+  uint16_t* wh = reinterpret_cast<uint16_t*>(workspace);
+  uint16_t* wl = wh + packed_halfs(g);
+  double* part = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + stats_packed_bytes(stride, Cin, Cout, PREC));
+  hipLaunchKernelGGL((dd_conv_pack_kernel<PREC, RAGGED>), dim3(blocks_for(packed_halfs(g))), dim3(kThreads), 0, st, w, wh, wl, g.pack_mode, g.N, g.K,
+                     g.taps, g.kstep);
+  const int tiles_x = (Wo + kTileW - 1) / kTileW, tiles_y = (Ho + kTileH - 1) / kTileH;
+  const dim3 grid((unsigned)tiles_x * (unsigned)tiles_y, (unsigned)((g.N + kTileN - 1) / kTileN), (unsigned)B);
+  if (stride == 2) {
+    constexpr GemmKind k = gemm_kind(kOpConv3S2, 0);
+    hipLaunchKernelGGL((dd_conv_igemm_stats_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>), grid, dim3(kThreads), 0, st, x,
+                       (const uint16_t*)wh, (const uint16_t*)wl, y, g.K, g.N, H, W, Ho, Wo, tiles_x, bias, part);
+  } else {
+    constexpr GemmKind k = gemm_kind(kOpConv3, 0);
+    hipLaunchKernelGGL((dd_conv_igemm_stats_kernel<PREC, k.ks, k.stride, k.pad, k.kstep, k.scatter, RAGGED>), grid, dim3(kThreads), 0, st, x,
+                       (const uint16_t*)wh, (const uint16_t*)wl, y, g.K, g.N, H, W, Ho, Wo, tiles_x, bias, part);
+  }
+  hipLaunchKernelGGL(dd_conv_stats_combine_kernel, dim3((unsigned)Cout), dim3(kThreads), 0, st, (const double*)part, sums, B * tiles_x * tiles_y, Cout,
+                     (double)B * (double)Ho * (double)Wo);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------------------------
@@ -583,6 +658,21 @@ hipError_t launch_conv_affine(int stride, const float* x, const float* w, const 
   return dispatch(prec, Cin, Cout, false, [&](auto p, auto ragged, auto) {
     return launch_affine_prec<decltype(p)::value, decltype(ragged)::value>(stride, x, w, scale_shift, addend, y, workspace, relu, B, Cin, Cout, H, W,
                                                                            st);
+  });
+}
+
+// ---- the statistics-emitting forward ------------------------------------------------------------------------------------------------------------------
+size_t workspace_bytes_stats(int stride, int B, int Cin, int Cout, int H, int W, int prec) {
+  const int Ho = stride == 2 ? strided_out(H) : H, Wo = stride == 2 ? strided_out(W) : W;
+  const size_t tiles = (size_t)((Wo + kTileW - 1) / kTileW) * (size_t)((Ho + kTileH - 1) / kTileH);
+  const size_t partials = (size_t)Cout * (size_t)B * tiles * 2 * sizeof(double);
+  return stats_packed_bytes(stride, Cin, Cout, prec) + (partials + 255) / 256 * 256;
+}
+
+hipError_t launch_conv_stats(int stride, const float* x, const float* w, const float* bias, float* y, double* sums, void* workspace, int B, int Cin,
+                             int Cout, int H, int W, int prec, hipStream_t st) {
+  return dispatch(prec, Cin, Cout, false, [&](auto p, auto ragged, auto) {
+    return launch_stats_prec<decltype(p)::value, decltype(ragged)::value>(stride, x, w, bias, y, sums, workspace, B, Cin, Cout, H, W, st);
   });
 }
 

@@ -1,6 +1,6 @@
 // dd_conv_kernels.h -- the GEMM kernels of csrc/dd_conv.hip, written ONCE and included there TWICE (and a third time, DD_CONV_BIAS 1, for the biased
-// forward of include/ddepth_conv_strided.h alone, and a fourth, DD_CONV_AFFINE 1, for the folded eval-mode forward of include/ddepth_conv_fused.h
-// alone: below): with DD_CONV_SCALED 0 it defines the kernels of include/ddepth_conv.h and ddepth_conv_strided.h
+// forward of include/ddepth_conv_strided.h alone, a fourth, DD_CONV_AFFINE 1, for the folded eval-mode forward of include/ddepth_conv_fused.h
+// alone, and a fifth, DD_CONV_STATS 1, for the statistics-emitting training forward of include/ddepth_conv_stats.h alone: below): with DD_CONV_SCALED 0 it defines the kernels of include/ddepth_conv.h and ddepth_conv_strided.h
 // (dd_conv_igemm_kernel, dd_conv_wgrad_kernel, dd_conv1x1_gemm_kernel, dd_conv1x1_wgrad_kernel, dd_conv_wgrad_reduce_kernel, dd_conv_s2_dgrad_kernel,
 // dd_conv_bias_grad_kernel, dd_conv_bias_grad_reduce_kernel), with
 // DD_CONV_SCALED 1 their twins *_scaled_kernel of include/ddepth_conv_scaled.h, which take the device pair scale = {s, 1 / s} as one more (last)
@@ -40,6 +40,16 @@
 #define DD_CONV_GY(is_grad_y, v) (v)
 #define DD_CONV_UNSCALED(v) (v)
 #define DD_CONV_EPILOGUE(v, n, o) affine_tail(fmaf((v), scale_shift[n], scale_shift[N + (n)]), addend, (o), relu)
+#elif DD_CONV_STATS
+// a fifth pass (include/ddepth_conv_stats.h): dd_conv_igemm_stats_kernel alone, the implicit GEMM of the bias pass (bias[N] or NULL, the same add where
+// the accumulator is stored) with one more argument, part[N][B][tiles][2] in fp64: per workgroup and output channel of its tile the sum of the STORED
+// fp32 values of the tile's pixels inside the Ht x Wt grid and the sum of their squares -- what dd_bn_stats would read back from `out`.  The
+// epilogue of this pass is its own text below (every lane reaches its barriers); the other passes keep theirs.
+#define DD_CONV_KERNEL(name) name##_stats_kernel
+#define DD_CONV_SCALE_PARAM , const float* __restrict__ bias, double* __restrict__ part
+#define DD_CONV_GY(is_grad_y, v) (v)
+#define DD_CONV_UNSCALED(v) (v)
+#define DD_CONV_EPILOGUE(v, n, o) (bias ? (v) + bias[n] : (v))
 #else
 #define DD_CONV_KERNEL(name) name##_kernel
 #define DD_CONV_SCALE_PARAM
@@ -124,6 +134,62 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_igemm)(const 
 
   // accumulator entry r of lane l: column (pixel) l % 32, row (output channel) 8 * (r / 4) + 4 * (l / 32) + r % 4
   const int y = ty * kTileH + wave, x = tx * kTileW + l32;
+#if DD_CONV_STATS
+  // Store as the bias pass stores, and sum what is stored.  The patch is dead behind the main loop: the tile's fp32 values are staged there, CH
+  // output channels at a time (as many of 64 / 32 / 16 as the patch of this instantiation holds), a channel a row of 128 pixels (pixel p at float
+  // p + p / 16: the strips below start in different banks); a pixel outside the grid is staged as +0.0 by a SELECT -- its accumulator holds real
+  // neighbour sums.  Then 256 / CH threads per channel add one strip of 128 / (256 / CH) consecutive pixels each, in pixel order, in fp64 (the
+  // square of a widened fp32 is exact), and an xor tree over those neighbouring lanes adds the strips: one fixed order, no atomics.  Every lane
+  // reaches every barrier and shuffle; a row n >= N of a RAGGED instantiation reads no bias and writes no partial.
+  static_assert(!SCATTER, "the stats pass is the plain 3x3 forward");
+  constexpr int kRow = kTileH * kTileW + kTileH * kTileW / 16;      // floats per staged channel
+  constexpr int kPatchBytes = (int)sizeof(uint16_t) * NL * PP * PS;
+  constexpr int CH = kPatchBytes >= 64 * kRow * 4 ? 64 : kPatchBytes >= 32 * kRow * 4 ? 32 : 16;
+  static_assert(kPatchBytes >= CH * kRow * 4, "the patch holds one staging pass");
+  constexpr int TPC = kThreads / CH, SL = kTileH * kTileW / TPC;      // threads per channel, pixels per strip
+  float* stage = reinterpret_cast<float*>(&patch[0][0]);
+  const bool inside = y < Ht && x < Wt;
+  const int pix = wave * kTileW + l32;
+#pragma unroll
+  for (int p = 0; p < kTileN / CH; ++p) {
+    __syncthreads();      // the main loop's reads of the patch (the previous pass's reads of the stage) are over
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        if ((nb * 32 + 8 * (r / 4)) / CH != p) continue;      // (known where the loops are unrolled)
+        const int cl = nb * 32 + 8 * (r / 4) + 4 * half + (r % 4), n = n0 + cl;
+        float v = acc[nb][r];
+        if (!RAGGED || n < N) {
+          v = DD_CONV_EPILOGUE(DD_CONV_UNSCALED(v), n, 0);
+          if (inside) out[(((size_t)b * N + n) * Ht + y) * (size_t)Wt + x] = v;
+        }
+        stage[(cl - p * CH) * kRow + pix + (pix >> 4)] = inside ? v : 0.0f;
+      }
+    }
+    __syncthreads();
+    const int c = tid / TPC, s = tid % TPC;
+    const float* strip = stage + c * kRow + s * SL + (s * SL >> 4);
+    double sa = 0.0, sb = 0.0;
+#pragma unroll
+    for (int i = 0; i < SL; ++i) {
+      const double d = (double)strip[i + (i >> 4)];
+      sa += d;
+      sb += d * d;
+    }
+#pragma unroll
+    for (int d = 1; d < TPC; d <<= 1) {
+      sa += __shfl_xor(sa, d);
+      sb += __shfl_xor(sb, d);
+    }
+    const int n = n0 + p * CH + c;
+    if (s == 0 && (!RAGGED || n < N)) {
+      double* dst = part + (((size_t)n * gridDim.z + b) * gridDim.x + blockIdx.x) * 2;
+      dst[0] = sa;
+      dst[1] = sb;
+    }
+  }
+#else
   if (y >= Ht || x >= Wt) return;
 #pragma unroll
   for (int nb = 0; nb < 2; ++nb) {
@@ -144,9 +210,10 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_igemm)(const 
       }
     }
   }
+#endif      // DD_CONV_STATS
 }
 
-#if !DD_CONV_BIAS && !DD_CONV_AFFINE      // (the bias and the affine pass: the implicit GEMM alone)
+#if !DD_CONV_BIAS && !DD_CONV_AFFINE && !DD_CONV_STATS      // (the bias, the affine and the stats pass: the implicit GEMM alone)
 // ---- weight gradient --------------------------------------------------------------------------------------------------------------------------------
 // P [B][Cp][Hp][Wp] is read at the pixel itself, Q [B][Cq][Hq][Wq] at (y * S - PAD + ky, x * S - PAD + kx):
 //   3x3:        P = grad_y, Q = x       -> grad_w[co][ci][ky][kx]          transpose convolution:  P = x, Q = grad_y -> grad_w[ci][co][dy][dx]
@@ -583,7 +650,7 @@ __global__ __launch_bounds__(kThreads) void DD_CONV_KERNEL(dd_conv_bias_grad_red
   for (int k = 1; k < chunks; ++k) s += part[(size_t)co * chunks + k];
   grad_bias[co] = DD_CONV_UNSCALED((float)s);
 }
-#endif      // !DD_CONV_BIAS && !DD_CONV_AFFINE
+#endif      // !DD_CONV_BIAS && !DD_CONV_AFFINE && !DD_CONV_STATS
 
 #undef DD_CONV_KERNEL
 #undef DD_CONV_SCALE_PARAM

@@ -19,7 +19,7 @@ from torch import nn
 from . import modules as _modules
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm, resolve_bn_backend
 from .codec import convert_hip_codec, resolve_codec_backend
-from .conv import convert_hip_conv, resolve_conv_backend, resolve_conv_grad_autoscale
+from .conv import conv_bn_train, convert_hip_conv, resolve_conv_backend, resolve_conv_bn_stats, resolve_conv_grad_autoscale
 from .modules import CNNDDIMPipiline, CNNDDIMPipilineVis, DeepDepthTransformWithUpsampling, HipBound, ScheduledCNNRefine
 from .necks import HAHIHeteroNeck
 from .scheduler import DDIMScheduler
@@ -52,7 +52,7 @@ class DDIMDepthEstimate_Res(nn.Module):
 
     def __init__(self, in_channels=(64, 128, 256, 512), up_scale_factor=1, inference_steps=20, num_train_timesteps=1000,
                  return_indices=None, depth_transform_cfg=None, depth_feature_dim=16, detach_fp=False, loss_cfgs=(),
-                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, codec_backend=None, conv_grad_autoscale=None, **kwargs):
+                 init_cfg=None, precision=None, condition_backend="hip", eval_ddim_loss=True, loss_noise_device=None, profile=None, bn_backend=None, conv_backend=None, codec_backend=None, conv_grad_autoscale=None, conv_bn_stats=None, **kwargs):
         """Beyond the reference's keywords (src/model/diffusion_dcbase_model.py:77-91):
         profile            the two shipped configurations of a head (PROFILES below; None = $DDEPTH_PROFILE, else "reference"):
                              "reference" [default]  what the reference does, bit for bit where that is defined: fp32 arithmetic (the reference runs
@@ -96,7 +96,13 @@ class DDIMDepthEstimate_Res(nn.Module):
         codec_backend      "torch" [default] or "hip" (None = $DDEPTH_CODEC_BACKEND, else "torch"): with "hip" the four convolutions of
                            ``depth_transform`` become codec.HipCodecConv2d / codec.HipCodecConvTranspose2d holding the same tensors and the
                            decoder's nn.Sigmoid a codec.HipCodecTail, so their .train() forward and backward run in csrc/dd_codec.hip in
-                           fp32, whatever `precision` is (same state-dict keys; the eval-mode dd_encode / dd_decode unchanged)."""
+                           fp32, whatever `precision` is (same state-dict keys; the eval-mode dd_encode / dd_decode unchanged).
+        conv_bn_stats      False [default] or True (None = $DDEPTH_CONV_BN_STATS, "1" is on): where a conv_lateral is a conv.HipConv2d followed by
+                           a batchnorm.HipBatchNorm2d (`conv_backend="hip*"` with `bn_backend="hip"` / "hip+add"), the .train() pair runs through
+                           conv.conv_bn_train: the convolution's epilogue emits the BatchNorm's statistics (include/ddepth_conv_stats.h), the
+                           "hip+add" addend included, whose statistics are those of the convolution's output alone.  Any other site runs what
+                           it ran.  Parameter tensors, state-dict keys and child indices are unchanged.  conv_up (a transpose convolution), the
+                           neck's pointwise convolutions and the codec are not covered."""
         super().__init__()
         profile = profile or os.environ.get("DDEPTH_PROFILE") or "reference"      # (an empty DDEPTH_PROFILE means "not set")
         if profile not in PROFILES:
@@ -179,6 +185,7 @@ class DDIMDepthEstimate_Res(nn.Module):
             for name in ("conv_lateral", "conv_up", "convup_fp"):
                 if hasattr(self, name):
                     setattr(self, name, convert_hip_conv(getattr(self, name), precision, False, channels, *autoscale))
+        self.conv_bn_stats = resolve_conv_bn_stats(conv_bn_stats)
         self.codec_backend = resolve_codec_backend(codec_backend)
         if self.codec_backend == "hip":
             convert_hip_codec(self.depth_transform)
@@ -213,13 +220,33 @@ class DDIMDepthEstimate_Res(nn.Module):
             f = fp[n - i - 1]
             lateral = self.conv_lateral[n - i - 1]
             if i > 0 and self.bn_backend == "hip+add":
-                cur = self._lateral_add(lateral, f, self.conv_up[n - i - 1](x))
+                top = self.conv_up[n - i - 1](x)
+                cur = self._lateral_stats(lateral, f, top) if self.conv_bn_stats else None
+                if cur is None:
+                    cur = self._lateral_add(lateral, f, top)
             else:
-                cur = lateral(f)
+                cur = self._lateral_stats(lateral, f) if self.conv_bn_stats else None
+                if cur is None:
+                    cur = lateral(f)
                 if i > 0:
                     cur = cur + F.adaptive_avg_pool2d(self.conv_up[n - i - 1](x), output_size=cur.shape[-2:])
             x = cur
         return x
+
+    @staticmethod
+    def _lateral_stats(lateral, f, top=None):
+        """``lateral(f)`` -- with ``top``: plus ``top``, added inside the BatchNorm's apply as ``_lateral_add`` does -- where the convolution is a
+        ``HipConv2d`` followed by a ``HipBatchNorm2d``, through conv.conv_bn_train: the convolution's epilogue emits the BatchNorm's statistics
+        (those of the convolution's output alone, whatever is added behind).  None, with nothing touched, anywhere else: the caller runs what
+        it ran."""
+        if len(lateral) != 3:
+            return None
+        if top is None:
+            out = conv_bn_train(lateral[0], lateral[1], f)
+            return lateral[2](out) if out is not None else None      # (nn.Identity where the BatchNorm carries the ReLU)
+        if getattr(lateral[1], "add_mode", None) == "post" and type(lateral[2]) is nn.Identity:
+            return conv_bn_train(lateral[0], lateral[1], f, addend=top)      # (None unless top has the lateral map's size: the pool is the identity)
+        return None
 
     @staticmethod
     def _lateral_add(lateral, f, top):

@@ -7,7 +7,8 @@ model can run offline with random-init weights.  Opt-in (``args.backbone_backend
 DDEPTH_BACKBONE_BACKEND=hip): the backbone's convolutions run in the library (conv.convert_hip_conv
 with ``channels="any", strided=True``); the default leaves the backbone as it is.  ``"hip+bn"`` adds the
 BatchNorms with the block tails fused for .train(), ``"hip+fold"`` also runs every BasicBlock in .eval() under
-no_grad as convolutions with BatchNorm, add and ReLU in their epilogues; ``args.backbone_precision`` /
+no_grad as convolutions with BatchNorm, add and ReLU in their epilogues, ``"hip+stats"`` also takes the training
+BatchNorms' statistics from the convolutions' epilogues; ``args.backbone_precision`` /
 DDEPTH_BACKBONE_PRECISION gives the backbone a precision of its own.
 """
 from __future__ import annotations
@@ -19,7 +20,7 @@ import torch
 from torch import nn
 
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
-from .conv import conv_bn_act, convert_hip_conv
+from .conv import conv_bn_act, conv_bn_train, convert_hip_conv
 from .head import build_head
 
 
@@ -38,6 +39,9 @@ class _BasicBlock(nn.Module):
         # set by fold_eval_basic_blocks: in .eval() without grad the block is two or three library calls (conv.conv_bn_act), each a convolution with the
         # folded BatchNorm, the residual add and the ReLU in its epilogue
         self.folded_eval = False
+        # set by fuse_conv_bn_stats: with fused_tail, in .train() each conv -> BatchNorm pair runs through conv.conv_bn_train -- the convolution's
+        # epilogue emits the BatchNorm's statistics, so no pass over its output starts the BatchNorm
+        self.conv_bn_stats = False
 
     def _forward_folded(self, x):
         """The eval-mode block in the library, or None where one of its calls is not native (nothing has been changed then)."""
@@ -55,6 +59,13 @@ class _BasicBlock(nn.Module):
             if out is not None:
                 return out
         idt = x if self.downsample is None else self.downsample(x)
+        if self.fused_tail and self.conv_bn_stats and self.training:
+            # (a pair that is not native -- CPU tensors, another module, an unsupported shape -- returns None untouched and runs as below)
+            out = conv_bn_train(self.conv1, self.bn1, x)
+            if out is None:
+                out = self.bn1(self.conv1(x))
+            res = conv_bn_train(self.conv2, self.bn2, out, addend=idt)
+            return res if res is not None else self.bn2(self.conv2(out), addend=idt)
         if self.fused_tail:
             out = self.bn1(self.conv1(x))
             return self.bn2(self.conv2(out), addend=idt)
@@ -146,7 +157,20 @@ def fold_eval_basic_blocks(backbone: nn.Module) -> nn.Module:
     return backbone
 
 
-BACKBONE_BACKENDS = ("torch", "hip", "hip+bn", "hip+fold")
+def fuse_conv_bn_stats(backbone: nn.Module) -> nn.Module:
+    """Marks every ``_BasicBlock`` of ``backbone`` ``conv_bn_stats``: in .train(), where the block has a fused tail (``fuse_basic_block_tails``),
+    ``conv1 + bn1`` and ``conv2 + bn2(+ identity)`` run through conv.conv_bn_train -- the convolutions of include/ddepth_conv_stats.h, whose
+    epilogues emit the BatchNorms' statistics, so that neither BatchNorm starts with a pass over its input.  A pair that is not native (CPU
+    tensors, a convolution or BatchNorm that is not the library's, an unsupported shape or precision) and everything in .eval() run exactly
+    what they ran.  The ``downsample`` convolution has no BatchNorm and is not touched.  Parameter tensors and state-dict keys are untouched;
+    calling it again changes nothing."""
+    for m in backbone.modules():
+        if isinstance(m, _BasicBlock):
+            m.conv_bn_stats = True
+    return backbone
+
+
+BACKBONE_BACKENDS = ("torch", "hip", "hip+bn", "hip+fold", "hip+stats")
 BACKBONE_PRECISIONS = ("bf16", "f16", "f16x3")
 
 
@@ -155,7 +179,8 @@ def resolve_backbone_backend(backbone_backend=None) -> str:
     convolutions run in the library, the stride-2 openings of every stage included), "hip+bn" ("hip", and at every precision the backbone's
     BatchNorms run in the library with each BasicBlock's ReLUs and residual add fused: convert_hip_batchnorm + fuse_basic_block_tails) or
     "hip+fold" ("hip+bn", and in .eval() without grad every BasicBlock runs its convolutions with BatchNorm, residual add and ReLU folded into
-    their epilogues: fold_eval_basic_blocks -- one value for training and inference)."""
+    their epilogues: fold_eval_basic_blocks -- one value for training and inference) or "hip+stats" ("hip+fold", and in .train() every
+    convolution of a BasicBlock that a BatchNorm follows emits that BatchNorm's statistics from its epilogue: fuse_conv_bn_stats)."""
     choice = backbone_backend or os.environ.get("DDEPTH_BACKBONE_BACKEND") or "torch"
     if choice not in BACKBONE_BACKENDS:
         raise ValueError(f"backbone_backend must be one of {list(BACKBONE_BACKENDS)} (got {choice!r})")
@@ -203,13 +228,16 @@ class Diffusion_DCbase_Model(nn.Module):
                 precision = getattr(getattr(self.depth_head, "model", None), "precision", None)
             self.depth_backbone = convert_hip_conv(self.depth_backbone, precision, channels="any", strided=True,
                                                    grad_autoscale=bool(getattr(self.depth_head, "conv_grad_autoscale", False)))
-        if self.backbone_backend in ("hip+bn", "hip+fold"):
+        if self.backbone_backend in ("hip+bn", "hip+fold", "hip+stats"):
             # BatchNorm is fp32 whatever the convolutions' precision: every BatchNorm of the backbone in the library, and in the bundled BasicBlock
             # stacks the two ReLUs and the residual add of each block inside those calls
             self.depth_backbone = fuse_basic_block_tails(convert_hip_batchnorm(self.depth_backbone))
-        if self.backbone_backend == "hip+fold":
+        if self.backbone_backend in ("hip+fold", "hip+stats"):
             # ... and in .eval() without grad each block's BatchNorms, add and ReLUs inside its convolutions' epilogues (include/ddepth_conv_fused.h)
             self.depth_backbone = fold_eval_basic_blocks(self.depth_backbone)
+        if self.backbone_backend == "hip+stats":
+            # ... and in .train() the BatchNorms' statistics out of the convolutions' epilogues (include/ddepth_conv_stats.h)
+            self.depth_backbone = fuse_conv_bn_stats(self.depth_backbone)
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125
