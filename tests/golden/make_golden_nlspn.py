@@ -18,9 +18,14 @@ Cases -> tests/golden/nlspn_<name>.npz
   as_noconf  affinity AS, --no_conf, prop_time 4
   tc_legacy  affinity TC with --legacy (offsets shifted in place), prop_time 3
   k5         prop_kernel 5 (24 neighbours), TGASS, prop_time 2
+  k7         prop_kernel 7 (48 neighbours), TGASS, 1 x 10 x 12, prop_time 2
+  ass        affinity ASS with the confidence, 2 x 9 x 14, prop_time 3
   dcn_*      plain modulated_deform_conv forward/backward cases (groups, deformable groups, stride, dilation) straight from the
              reference kernels, for the general DCNv2 entry points
-  dcn_device_cases   the seeded cases of tests/test_oracle_dcn.py (inputs + the reference kernels' forward / gradients)
+  dcn_device_cases   the seeded cases of tests/test_oracle_dcn.py (inputs + the reference kernels' forward / gradients), and "integer": the
+             integer-position inputs of tests/nlspn_cases.py (samples exactly on -1, 0, H - 1 and H)
+
+A file that exists is only overwritten after every array it holds has come out bit-identical again (_save): adding a case never moves an old one.
 """
 from __future__ import annotations
 
@@ -39,6 +44,17 @@ sys.path.insert(0, ROOT)
 
 from ref_import import REF_SRC, _install_stubs  # noqa: E402
 from oracle import dcn_ref  # noqa: E402
+
+
+def _save(path, out):
+    """np.savez_compressed, after asserting that every array of an existing file is reproduced bit for bit"""
+    if os.path.exists(path):
+        with np.load(path) as z:
+            for k in z.files:
+                new = np.asarray(out[k]) if k in out else None
+                assert new is not None and new.dtype == z[k].dtype and new.shape == z[k].shape and new.tobytes() == z[k].tobytes(), \
+                    f"{os.path.basename(path)}: existing array {k!r} would change"
+    np.savez_compressed(path, **out)
 
 
 def _install_dcn_standin():
@@ -106,7 +122,7 @@ def nlspn_case(NLSPN, name, seed, B, H, W, ch_g=8, k_f=3, prop_time=18, affinity
                    g_conv_weight=net.conv_offset_aff.weight.grad.numpy(), g_conv_bias=net.conv_offset_aff.bias.grad.numpy())
         if net.aff_scale_const.grad is not None:
             out["g_aff_scale_const"] = net.aff_scale_const.grad.numpy()
-    np.savez_compressed(os.path.join(HERE, f"nlspn_{name}.npz"), **out)
+    _save(os.path.join(HERE, f"nlspn_{name}.npz"), out)
     print(f"nlspn_{name}: |y| max {np.abs(out['y']).max():.3f}, |offset| max {np.abs(out['offset']).max():.2f}, "
           f"aff in [{out['aff'].min():.3f}, {out['aff'].max():.3f}]")
 
@@ -122,9 +138,9 @@ def dcn_case(name, seed, B, C, Co, H, W, kh, kw, stride, pad, dil, group, dg, st
     go = rs.standard_normal((B, Co, Ho, Wo)).astype(np.float32)
     y = dcn_ref.forward(x, w, b, off, m, stride, pad, dil, group, dg, step)
     gi, goff, gm, gw, gb = dcn_ref.backward(x, w, b, off, m, go, stride, pad, dil, group, dg, step)
-    np.savez_compressed(os.path.join(HERE, f"dcn_{name}.npz"), input=x, weight=w, bias=b, offset=off, mask=m, grad_out=go, out=y,
-                        g_input=gi, g_offset=goff, g_mask=gm, g_weight=gw, g_bias=gb,
-                        meta=np.array([stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, dg, step]))
+    _save(os.path.join(HERE, f"dcn_{name}.npz"), dict(input=x, weight=w, bias=b, offset=off, mask=m, grad_out=go, out=y,
+                                                      g_input=gi, g_offset=goff, g_mask=gm, g_weight=gw, g_bias=gb,
+                                                      meta=np.array([stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], group, dg, step])))
     print(f"dcn_{name}: out {y.shape}")
 
 
@@ -145,8 +161,15 @@ def device_code_cases():
     c = T._rand_case(np.random.RandomState(5), *shape)
     out.update({f"slip_{k}": v for k, v in c.items()})
     out["slip_g_input"] = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], shape[7], shape[8], shape[9], 1, 1)[0]
-    np.savez_compressed(os.path.join(HERE, "dcn_device_cases.npz"), **out)
-    print(f"dcn_device_cases: {len(T.SHAPES)} cases + the slip case")
+    import nlspn_cases as NC
+    B, C, Co, H, W, kh, kw, st, pd, dl, grp, dg = NC.DCN_CASES["integer"]
+    c = dict(zip(("x", "w", "b", "off", "m", "go"), NC.dcn_inputs("integer")))
+    out.update({f"integer_{k}": v for k, v in c.items()})
+    out["integer_out"] = dcn_ref.forward(c["x"], c["w"], c["b"], c["off"], c["m"], st, pd, dl, grp, dg, im2col_step=1)
+    g = dcn_ref.backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
+    out.update({f"integer_g_{k}": v for k, v in zip(T.GRAD_NAMES, g)})
+    _save(os.path.join(HERE, "dcn_device_cases.npz"), out)
+    print(f"dcn_device_cases: {len(T.SHAPES)} cases + the slip case + the integer-position case")
 
 
 def main():
@@ -157,6 +180,8 @@ def main():
     nlspn_case(NLSPN, "as_noconf", 13, 2, 9, 14, prop_time=4, affinity="AS", conf_prop=False, aff_gain=2.0, aff_bias=0.0)
     nlspn_case(NLSPN, "tc_legacy", 14, 1, 12, 10, prop_time=3, affinity="TC", legacy=True)
     nlspn_case(NLSPN, "k5", 15, 1, 14, 18, k_f=5, prop_time=2)
+    nlspn_case(NLSPN, "k7", 16, 1, 10, 12, k_f=7, prop_time=2)
+    nlspn_case(NLSPN, "ass", 17, 2, 9, 14, prop_time=3, affinity="ASS", aff_gain=2.0, aff_bias=0.0)
     dcn_case("groups", 21, 2, 4, 6, 7, 9, 3, 3, (1, 1), (1, 1), (1, 1), 2, 1, 1)
     dcn_case("dg_stride", 22, 2, 4, 4, 9, 8, 3, 3, (2, 1), (1, 1), (1, 2), 1, 2, 2)
     dcn_case("k1", 23, 3, 2, 3, 6, 5, 1, 1, (1, 1), (0, 0), (1, 1), 1, 1, 64)

@@ -736,7 +736,7 @@ def test_dcn_forward_backward_vs_reference_golden(lib, golden, name):
 AFFINITY_ID = {"AS": 0, "ASS": 1, "TC": 2, "TGASS": 3}
 
 
-@pytest.mark.parametrize("name", ["tgass", "preserve", "k5"] + (["as_noconf", "tc_legacy"] if FULL else []))
+@pytest.mark.parametrize("name", ["tgass", "preserve", "k5", "k7", "ass"] + (["as_noconf", "tc_legacy"] if FULL else []))
 def test_nlspn_refinement_vs_reference_golden(lib, golden, name):
     """conv_offset_aff (fp64 on the host here) -> dd_nlspn_offset_affinity -> dd_nlspn_propagate, against the goldens minted by the reference's NLSPN"""
     _bind_dcn(lib)
@@ -744,7 +744,7 @@ def test_nlspn_refinement_vs_reference_golden(lib, golden, name):
     B, H, W, ch_g, k_f, T, cp, pi, lg = [int(v) for v in g["meta"]]
     affinity = str(g["affinity"]) if "affinity" in g else None
     if affinity is None or affinity not in AFFINITY_ID:
-        affinity = {"tgass": "TGASS", "preserve": "TGASS", "k5": "TGASS", "as_noconf": "AS", "tc_legacy": "TC"}[name]
+        affinity = {"tgass": "TGASS", "preserve": "TGASS", "k5": "TGASS", "k7": "TGASS", "ass": "ASS", "as_noconf": "AS", "tc_legacy": "TC"}[name]
     num = k_f * k_f - 1
     oa = O.conv2d(g["guidance"].astype(np.float64), g["conv_weight"].astype(np.float64), g["conv_bias"].astype(np.float64)).astype(np.float32)
     oa = np.ascontiguousarray(oa)

@@ -39,7 +39,7 @@ def _module(g):
     return m
 
 
-@pytest.mark.parametrize("name", ["tgass", "preserve", "k5"])
+@pytest.mark.parametrize("name", ["tgass", "preserve", "k5", "k7", "ass"])
 def test_nlspn_module_fused_path_vs_reference_golden(dcn, lib, golden, name):
     g = golden("nlspn_" + name)
     m = _module(g).eval()

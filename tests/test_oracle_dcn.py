@@ -20,7 +20,7 @@ from oracle import dcn_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 2e-6
-NLSPN_CASES = ["tgass", "preserve", "as_noconf", "tc_legacy", "k5"]
+NLSPN_CASES = ["tgass", "preserve", "as_noconf", "tc_legacy", "k5", "k7", "ass"]
 
 
 def rel(a, b):
@@ -58,6 +58,21 @@ def test_oracle_matches_reference_device_code(golden, shape):
     g_or = O.mdcn_backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
     for name, a, r in zip(GRAD_NAMES, g_or, g_ref):
         assert rel(a, r) < TOL, name
+
+
+def test_oracle_matches_reference_device_code_at_integer_positions(golden):
+    """The integer-position inputs of tests/nlspn_cases.py (zero offsets on one image; samples exactly on -1, 0, H - 1 and H, where only the
+    strictness of the range test and the one-sided cell decide the offset gradient) through the reference's device code."""
+    import nlspn_cases as NC
+    B, C, Co, H, W, kh, kw, st, pd, dl, grp, dg = NC.DCN_CASES["integer"]
+    c = _device_case(golden, "integer")
+    for k, v in zip(("x", "w", "b", "off", "m", "go"), NC.dcn_inputs("integer")):
+        assert c[k].dtype == v.dtype and np.array_equal(c[k], v), k          # the fixture holds the inputs the kernels are given
+    NC.check_dcn_conditions()
+    assert rel(O.mdcn_forward(c["x"], c["w"], c["b"], c["off"], c["m"], st, pd, dl, grp, dg), c["out"]) < TOL
+    g_or = O.mdcn_backward(c["x"], c["w"], c["b"], c["off"], c["m"], c["go"], st, pd, dl, grp, dg)
+    for name, a in zip(GRAD_NAMES, g_or):
+        assert rel(a, c["g_" + name]) < TOL, name
 
 
 def test_reference_col2im_uses_pad_h_for_both_paddings(golden):

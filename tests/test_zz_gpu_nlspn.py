@@ -126,7 +126,7 @@ def test_dcn_reference_selftest_known_answers_and_errors(U):
         dcn.modulated_deform_conv_forward(x, w, b, off, ones, 3, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1)
 
 
-@pytest.mark.parametrize("name", ["tgass", "preserve", "as_noconf", "tc_legacy", "k5"])
+@pytest.mark.parametrize("name", ["tgass", "preserve", "as_noconf", "tc_legacy", "k5", "k7", "ass"])
 def test_nlspn_fused_path_matches_reference_goldens(U, golden, name):
     g = golden("nlspn_" + name)
     m = _module(g, U).eval()
@@ -232,7 +232,9 @@ def test_nlspn_full_size_properties(U):
     with pytest.raises(RuntimeError, match="built for ch_g 8"):
         dcn.nlspn_guided_offset_affinity(torch.zeros(1, 4, 8, 8, device="cuda"), torch.zeros(24, 4, 3, 3, device="cuda"), torch.zeros(24, device="cuda"),
                                          None, m.aff_scale_const, m.w_conf, m.b, 3, 3, "TGASS", False, False)
-    # (e) an odd width takes the one-pixel-per-lane kernel: same numbers as the 4-pixel kernel on the common columns' interior
+    # (e) an odd width (1213 = 18 whole tile columns + a last tile 61 wide) through the default kernel -- the LDS-window kernel, whatever the
+    # width: the four-pixels-per-lane kernel only runs under DD_NLSPN_KERNEL=g4 -- with zero offsets and identity affinities: still the
+    # identity.  (The kernels at ragged tiles with real offsets, and every DD_NLSPN_KERNEL variant: tests/test_zz_gpu_nlspn_cases.py.)
     Wc = W - 3
     crop = lambda t: t[..., :Wc].contiguous()
     fo = dcn.nlspn_propagate(crop(feat), torch.zeros(B, 18, H, Wc, device="cuda"), crop(aff0), None, w1, b0, 3, 2, False)
