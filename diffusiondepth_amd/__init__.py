@@ -28,7 +28,8 @@ from .loss import Diffusion_DCbase_Loss
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
 from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv, conv_bn_train
 from .codec import HipCodecConv2d, HipCodecConvTranspose2d, HipCodecTail, convert_hip_codec
-from .swin import HipShiftWindowMSA, convert_hip_window_attention, window_attention, window_attention_torch
+from .swin import (HipShiftWindowMSA, WindowAttentionFunction, convert_hip_window_attention, window_attention, window_attention_backward,
+                   window_attention_torch)
 
 __all__ = [
     "DDIMScheduler", "HipDenoiser", "precision_id", "library_path", "load_library",
@@ -38,6 +39,7 @@ __all__ = [
     "Diffusion_DCbase_Metric", "MetricAccumulator", "Diffusion_DCbase_Loss",
     "HipBatchNorm2d", "convert_hip_batchnorm", "fuse_basic_block_tails", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
     "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec", "fuse_conv_bn_stats", "conv_bn_train",
-    "HipShiftWindowMSA", "convert_hip_window_attention", "window_attention", "window_attention_torch",
+    "HipShiftWindowMSA", "convert_hip_window_attention", "window_attention", "window_attention_torch", "WindowAttentionFunction",
+    "window_attention_backward",
 ]
 __version__ = "0.1.0"

@@ -6,9 +6,13 @@
 
 #include <cstdint>
 
+namespace ddswin {
+__attribute__((visibility("hidden"))) thread_local ddstatus::LastError g_swin_err;      // shared with dd_api_swin_bwd.cpp: one dd_swin_last_error() for both headers
+}
+
 namespace {
 
-thread_local ddstatus::LastError g_swin_err;
+using ddswin::g_swin_err;
 
 int mode_of(int precision) { return precision == DD_PREC_FP32 ? 0 : precision == DD_PREC_BF16 ? 1 : precision == DD_PREC_F16 ? 2 : -1; }
 

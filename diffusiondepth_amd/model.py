@@ -12,7 +12,8 @@ BatchNorms' statistics from the convolutions' epilogues; ``args.backbone_precisi
 DDEPTH_BACKBONE_PRECISION gives the backbone a precision of its own.  Independent of it, ``args.backbone_attention="hip"`` /
 DDEPTH_BACKBONE_ATTENTION=hip runs every shifted-window attention of a Swin backbone (resolved or injected) as one library call in
 inference (swin.convert_hip_window_attention), at ``args.backbone_attention_precision`` / DDEPTH_BACKBONE_ATTENTION_PRECISION
-("fp32" by default, "bf16", "f16").
+("fp32" by default, "bf16", "f16"); ``"hip+train"`` also runs its backward in the library (``backward="hip"``), at "f16" with
+``args.backbone_attention_grad_autoscale`` / DDEPTH_BACKBONE_ATTENTION_GRAD_AUTOSCALE (on by default).
 """
 from __future__ import annotations
 
@@ -25,7 +26,7 @@ from torch import nn
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
 from .conv import conv_bn_act, conv_bn_train, convert_hip_conv
 from .head import build_head
-from .swin import convert_hip_window_attention, resolve_attention_backend, resolve_attention_precision
+from .swin import convert_hip_window_attention, resolve_attention_backend, resolve_attention_grad_autoscale, resolve_attention_precision
 
 
 class _BasicBlock(nn.Module):
@@ -243,11 +244,15 @@ class Diffusion_DCbase_Model(nn.Module):
             # ... and in .train() the BatchNorms' statistics out of the convolutions' epilogues (include/ddepth_conv_stats.h)
             self.depth_backbone = fuse_conv_bn_stats(self.depth_backbone)
         # Opt-in, independent of backbone_backend: the shifted-window attentions of a Swin backbone in the library (include/ddepth_swin.h) for
-        # inference.  Same parameter tensors, same state-dict keys; training and anything that needs a gradient keep the torch sequence.
+        # inference.  Same parameter tensors, same state-dict keys; training and anything that needs a gradient keep the torch sequence, unless
+        # "hip+train" asks for the library's backward (include/train/ddepth_swin_backward.h) as well.
         self.backbone_attention = resolve_attention_backend(getattr(self.args, "backbone_attention", None))
         self.backbone_attention_precision = resolve_attention_precision(getattr(self.args, "backbone_attention_precision", None))
-        if self.backbone_attention == "hip":
-            self.depth_backbone = convert_hip_window_attention(self.depth_backbone, self.backbone_attention_precision)
+        self.backbone_attention_grad_autoscale = resolve_attention_grad_autoscale(getattr(self.args, "backbone_attention_grad_autoscale", None))
+        if self.backbone_attention in ("hip", "hip+train"):
+            self.depth_backbone = convert_hip_window_attention(self.depth_backbone, self.backbone_attention_precision,
+                                                               backward="hip" if self.backbone_attention == "hip+train" else "torch",
+                                                               grad_autoscale=self.backbone_attention_grad_autoscale)
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125

@@ -1,4 +1,5 @@
-"""The Swin backbone's shifted-window attention over the C ABI of include/ddepth_swin.h: inference, window 7, head dimension 32.
+"""The Swin backbone's shifted-window attention over the C ABIs of include/ddepth_swin.h (forward) and include/train/ddepth_swin_backward.h
+(backward): window 7, head dimension 32.
 
 What it is for: the reference's ``ShiftWindowMSA`` (src/model/backbone/swin.py) runs pad -> roll -> mask build -> window partition -> ``qkv`` ->
 reshape / permute -> scale -> QK^T -> + relative-position bias -> + mask -> softmax -> .V -> transpose / reshape -> ``proj`` -> window reverse ->
@@ -10,6 +11,11 @@ library call that does the rest in its addressing (csrc/dd_swin.hip), and the ``
 The library route is decided BEFORE the call and taken only without autograd, for contiguous fp32 tensors on a HIP device, window 7,
 ``embed_dims == 32 * num_heads`` and no active dropout.  Everything else -- training, a tensor that needs a gradient, CPU tensors, other windows --
 runs the reference's sequence in torch (``window_attention_torch``, differentiable).  It is never a fallback after an error.
+
+Training, opt-in: ``backward="hip"`` (``convert_hip_window_attention(backbone, precision, backward="hip")``, ``args.backbone_attention =
+"hip+train"``) sends the differentiable case through ``WindowAttentionFunction``: the same forward call, and ONE backward call that recomputes
+the probabilities (csrc/dd_swin_bwd.hip) -- nothing of size [windows, heads, 49, 49] is saved.  The bias table's gradient is a fixed gather of
+the dense one (``fold_bias_grad``), so the whole route is bitwise reproducible.  The default ``backward="torch"`` changes nothing.
 """
 from __future__ import annotations
 
@@ -27,7 +33,10 @@ from . import backend
 ABI_SYMBOLS = ["dd_swin_last_error", "dd_window_attention_supported", "dd_window_attention_forward"]
 PRECISIONS = {"fp32": 1, "bf16": 2, "f16": 3}      # dd_precision
 WINDOW, HEAD_DIM = 7, 32
-ATTENTION_BACKENDS = ("torch", "hip")
+# every symbol include/train/ddepth_swin_backward.h declares (checked by tests/test_swin_backward_cpu.py)
+BACKWARD_ABI_SYMBOLS = ["dd_window_attention_backward_supported", "dd_window_attention_backward_workspace_bytes", "dd_window_attention_backward"]
+ATTENTION_BACKENDS = ("torch", "hip", "hip+train")
+BACKWARDS = ("torch", "hip")
 
 _bound = None
 
@@ -40,6 +49,10 @@ def _lib():
         lib.dd_swin_last_error.restype, lib.dd_swin_last_error.argtypes = ctypes.c_char_p, []
         lib.dd_window_attention_supported.restype, lib.dd_window_attention_supported.argtypes = c_int, [c_int] * 4
         lib.dd_window_attention_forward.restype, lib.dd_window_attention_forward.argtypes = c_int, [c_vp] * 4 + [c_int] * 8 + [c_vp]
+        lib.dd_window_attention_backward_supported.restype, lib.dd_window_attention_backward_supported.argtypes = c_int, [c_int] * 4
+        lib.dd_window_attention_backward_workspace_bytes.restype = c_int
+        lib.dd_window_attention_backward_workspace_bytes.argtypes = [c_int] * 7 + [ctypes.POINTER(ctypes.c_int64)]
+        lib.dd_window_attention_backward.restype, lib.dd_window_attention_backward.argtypes = c_int, [c_vp] * 9 + [c_int] * 8 + [c_vp]
         _bound = lib
     return _bound
 
@@ -186,6 +199,137 @@ def window_attention(qkv: torch.Tensor, qkv_pad: Optional[torch.Tensor], rel_bia
     return window_attention_torch(qkv, qkv_pad, rel_bias, heads, window, shift)
 
 
+# ---- the backward ------------------------------------------------------------------------------------------------------------------------------------
+def backward_workspace_bytes(B: int, H: int, W: int, C: int, heads: int, window: int = WINDOW, precision: str = "fp32") -> int:
+    """What dd_window_attention_backward_workspace_bytes answers (no device needed): a function of the shape alone."""
+    n = ctypes.c_int64(0)
+    rc = _lib().dd_window_attention_backward_workspace_bytes(int(B), int(H), int(W), int(C), int(heads), int(window), _precision_id(precision),
+                                                             ctypes.byref(n))
+    if rc != 0:
+        raise RuntimeError(f"dd_window_attention_backward_workspace_bytes failed ({rc}): {_lib().dd_swin_last_error().decode()}")
+    return int(n.value)
+
+
+_workspaces = {}      # (device, stream) -> a float tensor that only grows: calls on one stream are ordered, so they can share it
+
+
+def _workspace(nbytes: int, device: torch.device) -> torch.Tensor:
+    key = (device, int(torch.cuda.current_stream(device).cuda_stream))
+    ws = _workspaces.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        ws = _workspaces[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def window_attention_backward(qkv: torch.Tensor, qkv_pad: Optional[torch.Tensor], rel_bias: torch.Tensor, grad_out: torch.Tensor, heads: int,
+                              window: int, shift: int, precision: str = "fp32", scale: Optional[torch.Tensor] = None, need_pad: bool = True,
+                              need_bias: bool = True):
+    """One dd_window_attention_backward on contiguous fp32 HIP tensors -> (grad_qkv, grad_qkv_pad or None, grad_rel_bias [heads, 49, 49] or
+    None).  ``scale``: the 4-float tensor of ``conv.grad_scale`` for grad_out (read at "f16" only) or None.  The workspace is cached per device
+    and stream; nothing synchronises the host."""
+    for name, t in (("qkv", qkv), ("qkv_pad", qkv_pad), ("rel_bias", rel_bias), ("grad_out", grad_out), ("scale", scale)):
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise RuntimeError(f"{name} must be a contiguous fp32 tensor on a HIP device (got {t.dtype} on {t.device}); there is no CPU library path")
+    if qkv.dim() != 4 or qkv.shape[3] % 3:
+        raise ValueError(f"qkv must be [B, H, W, 3 C] (got {tuple(qkv.shape)})")
+    B, H, W, C = int(qkv.shape[0]), int(qkv.shape[1]), int(qkv.shape[2]), int(qkv.shape[3]) // 3
+    n = window * window
+    if tuple(rel_bias.shape) != (heads, n, n):
+        raise ValueError(f"rel_bias must be [{heads}, {n}, {n}] (got {tuple(rel_bias.shape)})")
+    if tuple(grad_out.shape) != (B, H, W, C):
+        raise ValueError(f"grad_out must be [{B}, {H}, {W}, {C}] (got {tuple(grad_out.shape)})")
+    if qkv_pad is not None and qkv_pad.numel() != 3 * C:
+        raise ValueError(f"qkv_pad must hold {3 * C} values (got {qkv_pad.numel()})")
+    if scale is not None and scale.numel() < 4:
+        raise ValueError("scale must be the 4-float tensor conv.grad_scale returns")
+    if qkv_pad is not None and qkv_pad.data_ptr() % 16:
+        qkv_pad = qkv_pad.clone()
+    if grad_out.data_ptr() % 16:
+        grad_out = grad_out.clone()
+    dev = qkv.device
+    grad_qkv = torch.empty_like(qkv)
+    grad_pad = torch.empty(3 * C, dtype=torch.float32, device=dev) if need_pad else None
+    grad_bias = torch.empty((heads, n, n), dtype=torch.float32, device=dev) if need_bias else None
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    with torch.cuda.device(dev):
+        ws = _workspace(backward_workspace_bytes(B, H, W, C, heads, window, precision), dev)
+        rc = _lib().dd_window_attention_backward(qkv.data_ptr(), ptr(qkv_pad), rel_bias.data_ptr(), grad_out.data_ptr(), grad_qkv.data_ptr(),
+                                                 ptr(grad_pad), ptr(grad_bias), ws.data_ptr(), ptr(scale), B, H, W, C, heads, window, shift,
+                                                 _precision_id(precision), int(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"dd_window_attention_backward failed ({rc}): {_lib().dd_swin_last_error().decode()}")
+    return grad_qkv, grad_pad, grad_bias
+
+
+class WindowAttentionFunction(torch.autograd.Function):
+    """``apply(qkv, qkv_pad, rel_bias, heads, window, shift, precision="fp32", grad_autoscale=True)``: dd_window_attention_forward (the bits of
+    ``window_attention_forward``) with dd_window_attention_backward as its gradient.  Saves qkv, qkv_pad and rel_bias only.  With
+    ``grad_autoscale`` the "f16" backward is preceded by dd_conv_grad_scale on grad_out (include/ddepth_conv_scaled.h).  Gradients: qkv, qkv_pad
+    and the DENSE bias; ``dense_bias_folded`` makes the table's gradient a fixed gather of the latter."""
+
+    @staticmethod
+    def forward(ctx, qkv, qkv_pad, rel_bias, heads, window, shift, precision="fp32", grad_autoscale=True):
+        out = window_attention_forward(qkv, qkv_pad, rel_bias, heads, window, shift, precision)
+        ctx.save_for_backward(qkv, qkv_pad, rel_bias)
+        ctx.cfg = (int(heads), int(window), int(shift), precision, bool(grad_autoscale))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qkv, qkv_pad, rel_bias = ctx.saved_tensors
+        heads, window, shift, precision, autoscale = ctx.cfg
+        grad_out = grad_out.contiguous()
+        scale = None
+        if precision == "f16" and autoscale:
+            from . import conv
+            scale = conv.grad_scale(grad_out, PRECISIONS["f16"])      # (dd_precision: the same enum)
+        need = ctx.needs_input_grad
+        gq, gp, gb = window_attention_backward(qkv, qkv_pad, rel_bias, grad_out, heads, window, shift, precision, scale,
+                                               need_pad=qkv_pad is not None and need[1], need_bias=need[2])
+        return (gq if need[0] else None), gp, gb, None, None, None, None, None
+
+
+_fold_cache = {}
+
+
+def bias_fold_index(window: int = WINDOW) -> torch.Tensor:
+    """[(2 window - 1)^2, window^2] (CPU, int64): for every row of the bias table the flat positions query * N + key of the dense [N, N] bias that
+    read it, in ascending order, padded with N * N -- the index of one appended zero."""
+    if window not in _fold_cache:
+        n = window * window
+        flat = relative_position_index(window).reshape(-1)
+        rows = torch.full(((2 * window - 1) ** 2, n), n * n, dtype=torch.int64)
+        for t in range(rows.shape[0]):
+            pos = torch.nonzero(flat == t).reshape(-1)
+            rows[t, :pos.numel()] = pos
+        _fold_cache[window] = rows
+    return _fold_cache[window]
+
+
+def fold_bias_grad(grad_dense: torch.Tensor, fold: torch.Tensor) -> torch.Tensor:
+    """The table's gradient [(2 window - 1)^2, heads] from the dense one [heads, N, N]: a gather and a sum in a fixed order, no scatter-add (whose
+    atomics would make the sum's order, and its bits, vary from run to run)."""
+    heads = grad_dense.shape[0]
+    padded = torch.cat([grad_dense.reshape(heads, -1), grad_dense.new_zeros(heads, 1)], dim=1)
+    return padded[:, fold].sum(-1).t().contiguous()
+
+
+class _DenseBias(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, table, index, fold):
+        ctx.fold = fold      # (a constant index, kept by the module: not a tensor saved for this backward)
+        return dense_bias(table, index)
+
+    @staticmethod
+    def backward(ctx, grad_dense):
+        return fold_bias_grad(grad_dense.contiguous(), ctx.fold), None, None
+
+
+def dense_bias_folded(table: torch.Tensor, index: torch.Tensor, fold: torch.Tensor) -> torch.Tensor:
+    """``dense_bias`` (the same bits) whose backward is ``fold_bias_grad``; ``fold``: ``bias_fold_index`` on the table's device."""
+    return _DenseBias.apply(table, index, fold)
+
+
 # ---- the module ------------------------------------------------------------------------------------------------------------------------------------
 class DropPath(nn.Module):
     """Stochastic depth per sample (the reference's default dropout_layer); the identity at drop_prob 0 or in .eval()."""
@@ -254,7 +398,7 @@ class HipShiftWindowMSA(nn.Module):
     Linear on the tokens as they are, one library call, the ``proj`` Linear and ``drop``; otherwise the reference's sequence in torch."""
 
     def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None, attn_drop_rate=0, proj_drop_rate=0,
-                 dropout_layer=dict(type="DropPath", drop_prob=0.), init_cfg=None, precision="fp32"):
+                 dropout_layer=dict(type="DropPath", drop_prob=0.), init_cfg=None, precision="fp32", backward="torch", grad_autoscale=True):
         super().__init__()
         self.window_size = window_size
         self.shift_size = shift_size
@@ -265,10 +409,13 @@ class HipShiftWindowMSA(nn.Module):
         self.init_cfg = init_cfg
         _precision_id(precision)
         self.precision = precision
+        self.backward = _backward_choice(backward)
+        self.grad_autoscale = bool(grad_autoscale)
         self._bias_cache = None
+        self._fold = None
 
     @classmethod
-    def from_module(cls, m: nn.Module, precision: str = "fp32") -> "HipShiftWindowMSA":
+    def from_module(cls, m: nn.Module, precision: str = "fp32", backward: str = "torch", grad_autoscale: bool = True) -> "HipShiftWindowMSA":
         """A HipShiftWindowMSA around the SAME ``w_msa`` and ``drop`` modules as the duck-typed ``m``: same tensors, same keys."""
         _precision_id(precision)
         new = cls.__new__(cls)
@@ -279,7 +426,10 @@ class HipShiftWindowMSA(nn.Module):
         new.drop = m.drop if isinstance(getattr(m, "drop", None), nn.Module) else nn.Identity()
         new.init_cfg = getattr(m, "init_cfg", None)
         new.precision = precision
+        new.backward = _backward_choice(backward)
+        new.grad_autoscale = bool(grad_autoscale)
         new._bias_cache = None
+        new._fold = None
         new.train(m.training)
         return new
 
@@ -308,11 +458,42 @@ class HipShiftWindowMSA(nn.Module):
             return False
         return supported(query.shape[-1], heads, self.window_size, self.precision)
 
+    def _train_route(self, query: torch.Tensor) -> bool:
+        """``backward="hip"`` and something needs a gradient: HIP fp32 tensors, window 7, head dimension 32, no autocast, an inactive attn_drop.
+        ``proj_drop`` and ``drop`` sit behind ``proj`` as torch modules and do not matter."""
+        w = self.w_msa
+        if self.backward != "hip" or not torch.is_grad_enabled():
+            return False
+        if not (query.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return False
+        if not (query.is_cuda and query.dtype == torch.float32 and w.qkv.weight.is_cuda and w.qkv.weight.dtype == torch.float32):
+            return False
+        if torch.is_autocast_enabled() or _active(getattr(w, "attn_drop", None), self.training):
+            return False
+        heads = int(w.num_heads)
+        if abs(float(w.scale) - HEAD_DIM ** -0.5) > 1e-12 or query.shape[-1] != HEAD_DIM * heads:
+            return False
+        return supported(query.shape[-1], heads, self.window_size, self.precision)
+
+    def _fold_index(self, device) -> torch.Tensor:
+        if self._fold is None or self._fold.device != device:
+            self._fold = bias_fold_index(self.window_size).to(device)
+        return self._fold
+
     def forward(self, query, hw_shape):
         B, L, C = query.shape
         H, W = hw_shape
         assert L == H * W, "input feature has wrong size"
         w = self.w_msa
+        if self._train_route(query):
+            qkv = w.qkv(query).view(B, H, W, 3 * C).contiguous()
+            table = w.relative_position_bias_table
+            bias = dense_bias_folded(table, w.relative_position_index, self._fold_index(table.device))
+            x = WindowAttentionFunction.apply(qkv, w.qkv.bias, bias, int(w.num_heads), self.window_size, self.shift_size, self.precision,
+                                              self.grad_autoscale)
+            x = w.proj(x.view(B, L, C))
+            proj_drop = getattr(w, "proj_drop", None)
+            return self.drop(proj_drop(x) if proj_drop is not None else x)
         if self._library_route(query):
             qkv = w.qkv(query).view(B, H, W, 3 * C)
             x = window_attention_forward(qkv.contiguous(), w.qkv.bias, self._dense_bias(), int(w.num_heads), self.window_size, self.shift_size,
@@ -349,6 +530,12 @@ class HipShiftWindowMSA(nn.Module):
         return self.drop(y.view(B, H * W, C))
 
 
+def _backward_choice(backward: str) -> str:
+    if backward not in BACKWARDS:
+        raise ValueError(f"backward must be one of {list(BACKWARDS)} (got {backward!r})")
+    return backward
+
+
 def _matches(m: nn.Module) -> bool:
     w = getattr(m, "w_msa", None)
     return hasattr(m, "window_size") and hasattr(m, "shift_size") and w is not None and \
@@ -364,25 +551,28 @@ def _convertible(m: nn.Module, precision: str) -> bool:
     return w.qkv.out_features == 3 * w.qkv.in_features and supported(w.qkv.in_features, int(w.num_heads), m.window_size, precision)
 
 
-def convert_hip_window_attention(module: nn.Module, precision: str = "fp32") -> nn.Module:
+def convert_hip_window_attention(module: nn.Module, precision: str = "fp32", backward: str = "torch", grad_autoscale: bool = True) -> nn.Module:
     """Replaces every duck-typed shifted-window attention of ``module`` (``window_size``, ``shift_size`` and a ``w_msa`` with ``qkv``, ``proj``,
     ``num_heads``, ``relative_position_bias_table``, ``relative_position_index`` -- the reference's own class included) that the operator runs by
     a ``HipShiftWindowMSA`` holding the SAME parameter and buffer tensors under the same keys.  Modules it does not run (another window, a head
-    dimension other than 32, a custom qk_scale) are left alone; calling it again changes nothing."""
+    dimension other than 32, a custom qk_scale) are left alone; calling it again changes nothing.  ``backward="hip"``: the converted modules
+    also run what needs a gradient in the library (``WindowAttentionFunction``), at "f16" with ``grad_autoscale``."""
     _precision_id(precision)
+    _backward_choice(backward)
     if isinstance(module, HipShiftWindowMSA):
         return module
     if _matches(module):
-        return HipShiftWindowMSA.from_module(module, precision) if _convertible(module, precision) else module
+        return HipShiftWindowMSA.from_module(module, precision, backward, grad_autoscale) if _convertible(module, precision) else module
     for name, child in list(module.named_children()):
-        new = convert_hip_window_attention(child, precision)
+        new = convert_hip_window_attention(child, precision, backward, grad_autoscale)
         if new is not child:
             setattr(module, name, new)
     return module
 
 
 def resolve_attention_backend(choice=None) -> str:
-    """``args.backbone_attention`` / DDEPTH_BACKBONE_ATTENTION: "torch" (default; empty or absent) or "hip"."""
+    """``args.backbone_attention`` / DDEPTH_BACKBONE_ATTENTION: "torch" (default; empty or absent), "hip" (inference) or "hip+train" ("hip" plus
+    ``backward="hip"``)."""
     choice = choice or os.environ.get("DDEPTH_BACKBONE_ATTENTION") or "torch"
     if choice not in ATTENTION_BACKENDS:
         raise ValueError(f"backbone_attention must be one of {list(ATTENTION_BACKENDS)} (got {choice!r})")
@@ -395,3 +585,19 @@ def resolve_attention_precision(choice=None) -> str:
     if choice not in PRECISIONS:
         raise ValueError(f"backbone_attention_precision must be one of {list(PRECISIONS)} (got {choice!r})")
     return choice
+
+
+def resolve_attention_grad_autoscale(choice=None) -> bool:
+    """``args.backbone_attention_grad_autoscale`` / DDEPTH_BACKBONE_ATTENTION_GRAD_AUTOSCALE: on by default; "0" / "false" / "off" / "no" or a
+    false value switch the f16 backward's rescale of grad_out off."""
+    if choice is None:
+        choice = os.environ.get("DDEPTH_BACKBONE_ATTENTION_GRAD_AUTOSCALE")
+    if choice is None or choice == "":
+        return True
+    if isinstance(choice, str):
+        if choice.lower() in ("1", "true", "on", "yes"):
+            return True
+        if choice.lower() in ("0", "false", "off", "no"):
+            return False
+        raise ValueError(f"backbone_attention_grad_autoscale must be a boolean (got {choice!r})")
+    return bool(choice)
