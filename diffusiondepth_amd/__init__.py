@@ -30,6 +30,7 @@ from .conv import HipConv2d, HipConvTranspose2d, convert_hip_conv, conv_bn_train
 from .codec import HipCodecConv2d, HipCodecConvTranspose2d, HipCodecTail, convert_hip_codec
 from .swin import (HipShiftWindowMSA, WindowAttentionFunction, convert_hip_window_attention, window_attention, window_attention_backward,
                    window_attention_torch)
+from .linear import HipFFN, convert_hip_swin_linears, linear_forward, pack_weight
 
 __all__ = [
     "DDIMScheduler", "HipDenoiser", "precision_id", "library_path", "load_library",
@@ -40,6 +41,6 @@ __all__ = [
     "HipBatchNorm2d", "convert_hip_batchnorm", "fuse_basic_block_tails", "HipConv2d", "HipConvTranspose2d", "convert_hip_conv",
     "HipCodecConv2d", "HipCodecConvTranspose2d", "HipCodecTail", "convert_hip_codec", "fuse_conv_bn_stats", "conv_bn_train",
     "HipShiftWindowMSA", "convert_hip_window_attention", "window_attention", "window_attention_torch", "WindowAttentionFunction",
-    "window_attention_backward",
+    "window_attention_backward", "HipFFN", "convert_hip_swin_linears", "linear_forward", "pack_weight",
 ]
 __version__ = "0.1.0"

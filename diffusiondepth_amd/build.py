@@ -16,11 +16,12 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libddepth_hip.so")
 SOURCES = ["dd_api.cpp", "dd_api_weights.cpp", "dd_api_plans.cpp", "dd_api_train.cpp", "dd_igemm2.hip", "dd_misc.hip", "dd_naive.hip", "dd_bwd.hip", "dd_wgrad.hip", "dd_wgrad2.hip", "dd_dcn.hip", "dd_thin.hip", "dd_msda.hip",
            "dd_api_eval.cpp", "dd_eval.hip", "dd_api_bn.cpp", "dd_bn.hip", "dd_api_conv.cpp", "dd_conv.hip", "dd_api_codec.cpp", "dd_codec.hip", "dd_api_swin.cpp", "dd_swin.hip",
-           "dd_api_swin_bwd.cpp", "dd_swin_bwd.hip"]
+           "dd_api_swin_bwd.cpp", "dd_swin_bwd.hip", "dd_api_linear.cpp", "dd_linear.hip"]
 # every header under csrc/ and include/ (a stale-check that misses one -- dd_gcn.h in round 1 -- reuses an old .so after an edit)
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + \
           [os.path.join("..", "..", "include", f) for f in sorted(os.listdir(os.path.join(HERE, "..", "include"))) if f.endswith(".h")] + \
-          [os.path.join("..", "..", "include", "train", "ddepth_swin_backward.h")]      # (a subdirectory: not in the listing above)
+          [os.path.join("..", "..", "include", "train", "ddepth_swin_backward.h"),      # (subdirectories: not in the listing above)
+           os.path.join("..", "..", "include", "swin", "ddepth_linear.h")]
 # -fno-slp-vectorize: hipcc otherwise packs adjacent scalar fp32 adds / multiplies into v_pk_add_f32 / v_pk_mul_f32, and packed fp32 VALU beside
 # running MFMAs costs ~22 cycles more per instruction than its two scalar halves (MI355X_MICROARCH.md; measured here: the 20-step loop 7.38 ->
 # 6.90 ms with this flag and scalar FMAs in the prologue, profiles/history/r02_run14_no_packed_fp32.md)

@@ -13,7 +13,10 @@ DDEPTH_BACKBONE_PRECISION gives the backbone a precision of its own.  Independen
 DDEPTH_BACKBONE_ATTENTION=hip runs every shifted-window attention of a Swin backbone (resolved or injected) as one library call in
 inference (swin.convert_hip_window_attention), at ``args.backbone_attention_precision`` / DDEPTH_BACKBONE_ATTENTION_PRECISION
 ("fp32" by default, "bf16", "f16"); ``"hip+train"`` also runs its backward in the library (``backward="hip"``), at "f16" with
-``args.backbone_attention_grad_autoscale`` / DDEPTH_BACKBONE_ATTENTION_GRAD_AUTOSCALE (on by default).
+``args.backbone_attention_grad_autoscale`` / DDEPTH_BACKBONE_ATTENTION_GRAD_AUTOSCALE (on by default).  ``args.backbone_linear="hip"`` /
+DDEPTH_BACKBONE_LINEAR=hip runs the Swin blocks' token Linears in the library for inference (linear.convert_hip_swin_linears: the FFNs, and
+qkv / proj of the converted attention modules), at ``args.backbone_linear_precision`` / DDEPTH_BACKBONE_LINEAR_PRECISION ("bf16" by default,
+"fp32", "f16").
 """
 from __future__ import annotations
 
@@ -26,6 +29,7 @@ from torch import nn
 from .batchnorm import HipBatchNorm2d, convert_hip_batchnorm
 from .conv import conv_bn_act, conv_bn_train, convert_hip_conv
 from .head import build_head
+from .linear import convert_hip_swin_linears, resolve_linear_backend, resolve_linear_precision
 from .swin import convert_hip_window_attention, resolve_attention_backend, resolve_attention_grad_autoscale, resolve_attention_precision
 
 
@@ -253,6 +257,13 @@ class Diffusion_DCbase_Model(nn.Module):
             self.depth_backbone = convert_hip_window_attention(self.depth_backbone, self.backbone_attention_precision,
                                                                backward="hip" if self.backbone_attention == "hip+train" else "torch",
                                                                grad_autoscale=self.backbone_attention_grad_autoscale)
+        # Opt-in, after the attention conversion: the token Linears of a Swin backbone in the library (include/swin/ddepth_linear.h) for inference --
+        # every duck-typed FFN (fc1 + GELU, fc2 + residual) and, in the attention modules converted above, qkv and proj.  With
+        # backbone_attention="torch" only the FFNs convert: the attention's Linears need the library attention module.
+        self.backbone_linear = resolve_linear_backend(getattr(self.args, "backbone_linear", None))
+        self.backbone_linear_precision = resolve_linear_precision(getattr(self.args, "backbone_linear_precision", None))
+        if self.backbone_linear == "hip":
+            self.depth_backbone = convert_hip_swin_linears(self.depth_backbone, self.backbone_linear_precision)
 
     def extract_depth(self, img, depth_map, depth_mask, gt_depth_map=None, return_loss=False, **kw):
         fp = self.depth_backbone(img)                                                   # :125

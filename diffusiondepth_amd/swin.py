@@ -28,6 +28,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import backend
+from . import linear as _linear
 
 # every symbol include/ddepth_swin.h declares (checked by tests/test_swin_cpu.py)
 ABI_SYMBOLS = ["dd_swin_last_error", "dd_window_attention_supported", "dd_window_attention_forward"]
@@ -395,10 +396,13 @@ def _active(drop: Optional[nn.Module], training: bool) -> bool:
 class HipShiftWindowMSA(nn.Module):
     """The reference's ShiftWindowMSA: same constructor keywords, attributes and state-dict keys (``w_msa.qkv.*``, ``w_msa.proj.*``,
     ``w_msa.relative_position_bias_table``, ``w_msa.relative_position_index``).  Without autograd on HIP fp32 tensors ``forward`` is the ``qkv``
-    Linear on the tokens as they are, one library call, the ``proj`` Linear and ``drop``; otherwise the reference's sequence in torch."""
+    Linear on the tokens as they are, one library call, the ``proj`` Linear and ``drop``; otherwise the reference's sequence in torch.
+    ``linear="hip"`` (``linear.convert_hip_swin_linears``) runs the two Linears of that inference branch in the library too, at
+    ``linear_precision``; the default ``linear="torch"`` changes nothing."""
 
     def __init__(self, embed_dims, num_heads, window_size, shift_size=0, qkv_bias=True, qk_scale=None, attn_drop_rate=0, proj_drop_rate=0,
-                 dropout_layer=dict(type="DropPath", drop_prob=0.), init_cfg=None, precision="fp32", backward="torch", grad_autoscale=True):
+                 dropout_layer=dict(type="DropPath", drop_prob=0.), init_cfg=None, precision="fp32", backward="torch", grad_autoscale=True,
+                 linear="torch", linear_precision=None):
         super().__init__()
         self.window_size = window_size
         self.shift_size = shift_size
@@ -411,6 +415,10 @@ class HipShiftWindowMSA(nn.Module):
         self.precision = precision
         self.backward = _backward_choice(backward)
         self.grad_autoscale = bool(grad_autoscale)
+        self.linear = _linear_choice(linear)
+        self.linear_precision = linear_precision      # (None: the attention's)
+        if linear_precision is not None:
+            _precision_id(linear_precision)
         self._bias_cache = None
         self._fold = None
 
@@ -428,6 +436,7 @@ class HipShiftWindowMSA(nn.Module):
         new.precision = precision
         new.backward = _backward_choice(backward)
         new.grad_autoscale = bool(grad_autoscale)
+        new.linear, new.linear_precision = "torch", None
         new._bias_cache = None
         new._fold = None
         new.train(m.training)
@@ -457,6 +466,20 @@ class HipShiftWindowMSA(nn.Module):
         if abs(float(w.scale) - HEAD_DIM ** -0.5) > 1e-12 or query.shape[-1] != HEAD_DIM * heads:
             return False
         return supported(query.shape[-1], heads, self.window_size, self.precision)
+
+    def _linear_route(self, query: torch.Tensor) -> bool:
+        """On the library route (``_library_route`` holds): ``linear="hip"``, a contiguous query, and ``qkv`` and ``proj`` plain Linears the
+        operator runs.  Otherwise they stay torch calls, as with ``linear="torch"``."""
+        if getattr(self, "linear", "torch") != "hip":
+            return False
+        w = self.w_msa
+        lp = self.linear_precision or self.precision
+        C = query.shape[-1]
+        if not _linear.linear_native(w.qkv, query, _linear.ACT_NONE, lp) or w.qkv.out_features != 3 * C:
+            return False
+        p = w.proj
+        return type(p) is nn.Linear and p.in_features == C and p.weight.is_cuda and p.weight.dtype == torch.float32 and \
+            p.weight.is_contiguous() and (p.bias is None or p.bias.is_contiguous()) and _linear.supported(C, p.out_features, _linear.ACT_NONE, lp)
 
     def _train_route(self, query: torch.Tensor) -> bool:
         """``backward="hip"`` and something needs a gradient: HIP fp32 tensors, window 7, head dimension 32, no autocast, an inactive attn_drop.
@@ -495,6 +518,15 @@ class HipShiftWindowMSA(nn.Module):
             proj_drop = getattr(w, "proj_drop", None)
             return self.drop(proj_drop(x) if proj_drop is not None else x)
         if self._library_route(query):
+            if self._linear_route(query):
+                # linear="hip": qkv and proj in the library as well (include/swin/ddepth_linear.h), their weights packed once
+                lp = self.linear_precision or self.precision
+                qkv = _linear.linear_forward(query, _linear.packed_for(self, "qkv", w.qkv, lp), w.qkv.bias, None, _linear.ACT_NONE, lp)
+                x = window_attention_forward(qkv.view(B, H, W, 3 * C), w.qkv.bias, self._dense_bias(), int(w.num_heads), self.window_size,
+                                             self.shift_size, self.precision)
+                x = _linear.linear_forward(x.view(B, L, C), _linear.packed_for(self, "proj", w.proj, lp), w.proj.bias, None, _linear.ACT_NONE, lp)
+                proj_drop = getattr(w, "proj_drop", None)
+                return self.drop(proj_drop(x) if proj_drop is not None else x)
             qkv = w.qkv(query).view(B, H, W, 3 * C)
             x = window_attention_forward(qkv.contiguous(), w.qkv.bias, self._dense_bias(), int(w.num_heads), self.window_size, self.shift_size,
                                          self.precision)
@@ -528,6 +560,12 @@ class HipShiftWindowMSA(nn.Module):
         if pad_r > 0 or pad_b:
             y = y[:, :H, :W, :].contiguous()
         return self.drop(y.view(B, H * W, C))
+
+
+def _linear_choice(linear: str) -> str:
+    if linear not in _linear.LINEAR_BACKENDS:
+        raise ValueError(f"linear must be one of {list(_linear.LINEAR_BACKENDS)} (got {linear!r})")
+    return linear
 
 
 def _backward_choice(backward: str) -> str:
